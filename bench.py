@@ -7,10 +7,17 @@
 
 One "step" = one full ``training_step`` (src/model.py:259-281: generator phase + discriminator
 phase, both AdamW updates) on one 1x24x128^3 volume per GPU, inputs resident in HBM.  W untimed
-warm-up steps, then (untimed, reported as ``settle_steps``) further steps until the GPU has been
-busy for ``--settle-s`` seconds so that the clock the chip holds under sustained MFMA load is reached,
-then EXACTLY K timed steps between barrier + synchronize pairs; MAX over ranks.  Rank 0 prints ONE JSON
-line (metric/unit from BASELINE.json) carrying
+warm-up steps, then ``--settle-steps`` further untimed steps (default 200, ~2 s of the 128^3 step) so that
+the clock the chip holds under sustained MFMA load is reached, then EXACTLY K timed steps between
+barrier + synchronize pairs; MAX over ranks.  Rank 0 prints ONE JSON line (metric/unit from BASELINE.json)
+with ``value`` and ``ms_per_step`` (milliseconds per timed step).  The settle phase is a fixed number of steps,
+not a duration: the model state after the last timed step then depends on the arguments alone.
+
+``--dump-outputs DIR`` writes, right after the timed steps, what a caller of the step holds after the last
+one (``dump_outputs``): the logged losses, each network's BatchNorm running statistics and a fixed, seeded
+sample of its updated parameters, as ``DIR/<name>.npy`` (float32 / float64, ~32 MB in all).
+
+``--full`` adds what takes runs of its own after the timed steps (a plain run measures the step time only):
 
 * ``roofline``     -- the dominant kernel family = the convolution plan with the largest summed duration
   (measured, not assumed): algorithmic FLOPs of all its launches / their summed duration, HIP events on
@@ -60,15 +67,17 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--settle-s", type=float, default=2.0, help="untimed extra steps until the GPU has run this long")
+    ap.add_argument("--settle-steps", type=int, default=200, help="untimed steps between the warm-up and the timed steps (clock steady state)")
+    ap.add_argument("--full", action="store_true", help="also the roofline probes and the CPU baseline (runs of their own after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--batch", type=int, default=1, help="volumes per GPU per step")
     ap.add_argument("--dtype", choices=["bf16", "f32", "fp8"], default="bf16")
     ap.add_argument("--workload", choices=["gan_step", "gen_only"], default="gan_step")
     ap.add_argument("--dropout", type=float, default=0.05)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--no-probe", action="store_true")
+    ap.add_argument("--no-probe", action="store_true", help="--full without the roofline probes")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend at world size > 1 (nccl = RCCL; gloo: rehearsal of the multi-rank path, ranks may share a GPU)")
     ap.add_argument("--no-graph", action="store_true", help="run the step eagerly instead of as hipGraph replays")
@@ -96,7 +105,10 @@ def parse():
     ap.add_argument("--small-norm-elements", type=int, default=None,
                     help="developer A/B: size limit of the one-launch norm kernels (0 = off); reported")
     ap.add_argument("--lib", default=None, help="developer A/B: another build of the C ABI (tools/diaglib.py); reported")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0 or a.settle_steps < 0:
+        ap.error("--steps must be >= 1, --warmup and --settle-steps >= 0")
+    return a
 
 
 class Probe:
@@ -233,6 +245,29 @@ def cpu_baseline(size, workload, nsteps):
                 sample=f"{len(times)} {workload} steps on one 1x24x{size}^3 volume after a 32^3 warm-up step "
                        f"({mean:.1f} s per step, min {min(times):.1f} / max {max(times):.1f}), torch CPU f32, "
                        "L1 + adversarial loss (no Perceptual term)")
+
+
+DUMP_SAMPLE = 1 << 22      # parameters kept per network: 16 MB of float32 (the two networks hold ~34 M, 135 MB)
+
+
+def dump_outputs(path, model):
+    """What a caller of the training step holds after the last timed step, as ``path/<name>.npy``: every logged loss
+    (float64 scalar), each network's BatchNorm running statistics and batch counters in full (``<net>_buffers``, float64)
+    and its parameters in state order, flattened and sampled at DUMP_SAMPLE positions drawn from a fixed seed
+    (``<net>_params``, float32)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in model.last_logs.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.asarray(float(v), dtype=np.float64))
+    for name, net in (("gen", model.gen), ("discr", model.discr)):
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+            if flat.numel() > DUMP_SAMPLE:
+                idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+                flat = flat[idx.to(flat.device)]
+            np.save(os.path.join(path, f"{name}_params.npy"), flat.cpu().numpy())
+            bufs = torch.cat([b.detach().reshape(-1).double() for b in net.buffers()])
+            np.save(os.path.join(path, f"{name}_buffers.npy"), bufs.cpu().numpy())
 
 
 def kernel_source_hash() -> str:
@@ -506,26 +541,16 @@ def main():
     for i in range(a.warmup):
         step(i)
     torch.cuda.synchronize()
-    # settle: keep the chip under the same load until it has been busy for --settle-s (clock / thermal steady state)
-    settle_steps = 0
-    t_s = time.perf_counter()
-    while True:
-        more = time.perf_counter() - t_s < a.settle_s
-        if world > 1:
-            # every rank must run the SAME number of steps (each step holds collectives): go on while any rank wants to
-            flag = torch.tensor([1.0 if more else 0.0], device=dev)
-            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-            more = bool(flag.item() > 0.0)
-        if not more:
-            break
-        for _ in range(5):
-            step(a.warmup + settle_steps)
-            settle_steps += 1
-        torch.cuda.synchronize()
+    # settle: keep the chip under the same load (clock / thermal steady state); every rank runs the same count
+    settle_steps = a.settle_steps
+    for i in range(settle_steps):
+        step(a.warmup + i)
+    torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    if mode == "eager" and not a.no_probe:
+    probing = a.full and not a.no_probe
+    if mode == "eager" and probing:
         ops.CONV_PROBE, ops.NORM_PROBE = probe.conv_probe, probe.norm_probe
         probe.enabled = True
     half = a.steps // 2
@@ -549,8 +574,10 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model)         # before the probe passes below, which run further steps
     probe_mode = "events around every launch of the kernel family inside the timed region"
-    if mode == "hipgraph" and not a.no_probe and rank == 0 and world == 1:
+    if mode == "hipgraph" and probing and rank == 0 and world == 1:
         # inside a graph replay single kernels cannot be bracketed with events: time the same launches
         # (same tensors, same kernels) in an eager replica pass right after the timed region
         gstep._eager_step()                 # unprobed: first eager pass after the replays (allocator, lazy state)
@@ -564,7 +591,7 @@ def main():
         probe.enabled = False
         probe_mode = "eager replica passes (3 steps) right after the hipGraph-timed region; mean over the passes per launch"
     ops.CONV_PROBE = ops.NORM_PROBE = None
-    if not a.no_probe:
+    if probing:
         probe.calibrate()
 
     if rank == 0:
@@ -619,7 +646,7 @@ def main():
                             "achieved": gbs, "frac": gbs / HBM_PEAK_GBS, "launches": s["launches"], "total_ms": s["total_ms"] / max(1, probe.passes),
                             "algorithmic_bytes": "2*C*V*b (read z, write a)" if kind == "fwd" else "3*C*V*b (read dy, read z, write dz; the two-kernel form executes 5 passes)"}
             out["roofline_hbm"] = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "kernels": hb, "measured": probe_mode}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.size, a.workload, a.cpu_steps)
         if real_stdout is not None:
             sys.stdout.flush()

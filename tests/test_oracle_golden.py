@@ -24,13 +24,28 @@ def _digest(module):
     return out
 
 
-def _check_digest(gold, prefix, module, rtol=1e-4, atol=1e-6):
+def _norm_fed_bias(tag, n):
+    """Conv biases directly in front of a normalisation: their gradient is analytically zero, what is computed is
+    rounding noise whose value depends on the CPU's summation order (AdamW turns its sign into a +-lr step)."""
+    if tag == "discr":
+        return n in ("d2.conv.bias", "d3.conv.bias", "d4.conv.bias", "d5.conv.bias")
+    return n.endswith("conv.bias") and "deconv" not in n and "final" not in n
+
+
+def _check_digest(gold, prefix, module, rtol=1e-4, atol=1e-6, zero=()):
     for n, v in _digest(module).items():
+        if n in zero:
+            continue
         ref = gold[f"{prefix}/{n}"]
         if v is None:
             assert np.isnan(ref).all(), n
         else:
-            np.testing.assert_allclose(v, ref, rtol=rtol, atol=atol, err_msg=n)
+            _check_sums(v, ref, rtol, atol, n)
+
+
+def _check_sums(v, ref, rtol, atol, n):
+    """[signed sum, abs sum] digests: the signed sum cancels, so it is compared on the scale of the abs sum."""
+    np.testing.assert_allclose(v, ref, rtol=0, atol=rtol * abs(ref[1]) + atol, err_msg=n)
 
 
 DS_CFGS = {
@@ -54,8 +69,10 @@ def test_downsample_conv_matches_reference(golden_dir, idx, name):
     (y * w).sum().backward()
     np.testing.assert_allclose(y.detach().numpy(), gold[f"{name}/y"], rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose(x.grad.numpy(), gold[f"{name}/dx"], rtol=1e-4, atol=1e-6)
-    _check_digest(gold, f"{name}/grad", m)
+    _check_digest(gold, f"{name}/grad", m, zero=("conv.bias",) if kw.get("batchnorm", True) else ())
     if kw.get("batchnorm", True):
+        # the conv bias feeds the BatchNorm: zero up to rounding, against the channel's gradient scale (measured ~1e-6)
+        assert m.conv.bias.grad.abs().max() <= 1e-5 * m.bn.bias.grad.abs().max()
         np.testing.assert_allclose(m.bn.running_mean.numpy(), gold[f"{name}/running_mean"], rtol=1e-5, atol=1e-7)
         np.testing.assert_allclose(m.bn.running_var.numpy(), gold[f"{name}/running_var"], rtol=1e-5, atol=1e-7)
         assert int(m.bn.num_batches_tracked) == 1
@@ -78,8 +95,13 @@ def test_discriminator_matches_reference(golden_dir, tag, modality, n, s, cin):
     loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, torch.ones_like(logits))
     loss.backward()
     np.testing.assert_allclose(logits.detach().numpy(), gold[f"{tag}/logits"], rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(y.grad[:, :, ::7, ::5, ::3].numpy(), gold[f"{tag}/dy_sample"], rtol=1e-4, atol=1e-9)
-    _check_digest(gold, f"{tag}/grad", d)
+    # atol on the gradient's own scale: f32 summation order moves its near-zero elements by ~1e-6 of its largest
+    ref = gold[f"{tag}/dy_sample"]
+    np.testing.assert_allclose(y.grad[:, :, ::7, ::5, ::3].numpy(), ref, rtol=1e-4, atol=2e-6 * np.abs(ref).max())
+    zero = [n for n, _ in d.named_parameters() if _norm_fed_bias("discr", n)]
+    _check_digest(gold, f"{tag}/grad", d, zero=zero)
+    for n in zero:                  # zero up to rounding, against the layer's weight gradient (measured ~2e-9)
+        assert d.get_parameter(n).grad.abs().sum() <= 1e-6 * d.get_parameter(n[:-4] + "weight").grad.abs().sum(), n
 
 
 def test_discriminator_param_count_bssfp():
@@ -132,21 +154,35 @@ def test_basic_unet_2d_plumbing_config():
 
 def test_gan_step_matches_reference(golden_dir):
     gold = _load(golden_dir, "gan_step.npz")
+    g64, spread = _load(golden_dir, "gan_step_f64.npz"), _load(golden_dir, "gan_step_f32_spread.npz")
     torch.manual_seed(0)
     gen = R.RefGenerator("bssfp", dropout=0.0).train()
     discr = R.RefDiscriminator("bssfp").train()
     g_opt, d_opt = R.make_optimizers(gen, discr)
     x, y = R.synthetic_batch(1, 64, seed=1234)
+    lr = g_opt.param_groups[0]["lr"]
     for step in range(2):
         logs = R.gan_training_step(gen, discr, g_opt, d_opt, x, y)
         for k, v in logs.items():
-            np.testing.assert_allclose(v.item(), gold[f"step{step}/{k}"], rtol=2e-4, err_msg=f"{step}/{k}")
-        for n, p in gen.named_parameters():
-            d = np.array([p.detach().double().sum().item(), p.detach().double().abs().sum().item()])
-            np.testing.assert_allclose(d, gold[f"step{step}/gen/{n}"], rtol=1e-3, atol=1e-4, err_msg=n)
-        for n, p in discr.named_parameters():
-            d = np.array([p.detach().double().sum().item(), p.detach().double().abs().sum().item()])
-            np.testing.assert_allclose(d, gold[f"step{step}/discr/{n}"], rtol=1e-3, atol=1e-4, err_msg=n)
+            key = f"step{step}/{k}"
+            if step == 0:
+                np.testing.assert_allclose(v.item(), gold[key], rtol=2e-4, err_msg=key)
+            else:
+                # after the first AdamW update f32 runs drift apart with the summation order: the yard-stick is f64 and
+                # the deviation an ensemble of f32 runs showed (as in tests/test_gpu_modules.py)
+                ref = float(g64[key])
+                assert abs(v.item() - ref) <= (3 * float(spread[key]) + 1e-7) * abs(ref), (key, v.item(), ref)
+        for tag, net in (("gen", gen), ("discr", discr)):
+            for n, p in net.named_parameters():
+                d = np.array([p.detach().double().sum().item(), p.detach().double().abs().sum().item()])
+                if _norm_fed_bias(tag, n):
+                    # each element took steps of at most lr whose signs rounding noise chose
+                    np.testing.assert_allclose(d, gold[f"step{step}/{tag}/{n}"], rtol=0, atol=2 * lr * p.numel() * (step + 1), err_msg=n)
+                else:
+                    # rounding noise also picks the AdamW sign of the small gradient elements of any parameter (~0.15 % of
+                    # them, tests/diag/diag_grad_noise.py; two in a 128-element BatchNorm bias): each lands 2 lr away
+                    flips = 2 * lr * (step + 1) * (4 + 0.002 * p.numel())
+                    _check_sums(d, gold[f"step{step}/{tag}/{n}"], 1e-3, 1e-4 + flips, n)
     # all parameters require grad again after the step (toggle/untoggle restored)
     assert all(p.requires_grad for p in gen.parameters())
     assert all(p.requires_grad for p in discr.parameters())

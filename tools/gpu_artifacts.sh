@@ -21,19 +21,19 @@ except Exception as e: print("$name", "ERR", e); print(open("gpurun_out/${tag}_b
 PY
 }
 if [[ $part == *b* ]]; then
-run bf16_default python bench.py
-run bf16_gen_only python bench.py --workload gen_only --no-cpu-baseline
-run bf16_160 python bench.py --size 160 --steps 100 --no-cpu-baseline
-run fp8_160 python bench.py --size 160 --steps 100 --dtype fp8 --no-cpu-baseline
-run bf16_8x64 python bench.py --size 64 --batch 8 --steps 100 --no-cpu-baseline
-run bf16_fresh_batch python bench.py --fresh-batch --no-cpu-baseline
-run bf16_force_collectives python bench.py --force-collectives --no-cpu-baseline
-run bf16_2rank_gloo python bench.py --gpus 2 --backend gloo --steps 20 --no-cpu-baseline
+run bf16_default python bench.py --full
+run bf16_gen_only python bench.py --full --workload gen_only --no-cpu-baseline
+run bf16_160 python bench.py --full --size 160 --steps 100 --no-cpu-baseline
+run fp8_160 python bench.py --full --size 160 --steps 100 --dtype fp8 --no-cpu-baseline
+run bf16_8x64 python bench.py --full --size 64 --batch 8 --steps 100 --no-cpu-baseline
+run bf16_fresh_batch python bench.py --full --fresh-batch --no-cpu-baseline
+run bf16_force_collectives python bench.py --full --force-collectives --no-cpu-baseline
+run bf16_2rank_gloo python bench.py --full --gpus 2 --backend gloo --steps 20 --no-cpu-baseline
 fi
 if [[ $part == *a* ]]; then
 # kernel stats of the eager step
 OUT=$ROOT/gpurun_out/${tag}_stats; mkdir -p $OUT
-( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o p -- python3 $ROOT/bench.py --steps 40 --warmup 5 --settle-s 0 --no-graph --no-cpu-baseline --no-probe > $OUT/run.log 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o p -- python3 $ROOT/bench.py --steps 40 --warmup 5 --settle-steps 0 --no-graph --no-cpu-baseline --no-probe > $OUT/run.log 2>&1 )
 cp $OUT/p_kernel_stats.csv gpurun_out/${tag}_bf16_default_kernel_stats.csv
 python3 tools/prof_summary.py $OUT 45 30 > gpurun_out/${tag}_bf16_default_summary.txt; head -9 gpurun_out/${tag}_bf16_default_summary.txt
 rm -f $OUT/p_kernel_trace.csv

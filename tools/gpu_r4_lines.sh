@@ -10,7 +10,7 @@ try:
 except Exception as e: print("$name", "ERR", e); print(open("gpurun_out/${tag}_bench_$name.err").read()[-600:])
 PY
 }
-run bf16_160 python bench.py --size 160 --steps 100 --no-cpu-baseline
-run fp8_160 python bench.py --size 160 --steps 100 --dtype fp8 --no-cpu-baseline
-run bf16_8x64 python bench.py --size 64 --batch 8 --steps 100 --no-cpu-baseline
-run bf16_force_collectives python bench.py --force-collectives --no-cpu-baseline
+run bf16_160 python bench.py --full --size 160 --steps 100 --no-cpu-baseline
+run fp8_160 python bench.py --full --size 160 --steps 100 --dtype fp8 --no-cpu-baseline
+run bf16_8x64 python bench.py --full --size 64 --batch 8 --steps 100 --no-cpu-baseline
+run bf16_force_collectives python bench.py --full --force-collectives --no-cpu-baseline

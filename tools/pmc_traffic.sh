@@ -10,6 +10,6 @@ OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT $ROOT/profiles
 cd /tmp && export TMPDIR=/tmp
 for name in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 400 rocprofv3 --pmc $name --kernel-trace --output-format csv -d $OUT/$name -o p -- python3 $ROOT/bench.py --size $SIZE --dtype $DTYPE --steps 2 --warmup 1 --settle-s 0 --no-graph --no-cpu-baseline --no-probe > $OUT/$name.log 2>&1 || { echo "pass $name failed"; tail -n 3 $OUT/$name.log; exit 1; }
+  timeout -k 10 400 rocprofv3 --pmc $name --kernel-trace --output-format csv -d $OUT/$name -o p -- python3 $ROOT/bench.py --size $SIZE --dtype $DTYPE --steps 2 --warmup 1 --settle-steps 0 --no-graph --no-cpu-baseline --no-probe > $OUT/$name.log 2>&1 || { echo "pass $name failed"; tail -n 3 $OUT/$name.log; exit 1; }
 done
 cd $ROOT && python3 tools/pmc_traffic.py $OUT $TAG $SIZE $DTYPE
