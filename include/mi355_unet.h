@@ -453,6 +453,32 @@ int mi355_dti_scalar_maps(const void* tensor, int32_t dtype, int64_t nvox, int64
                           void* rd, void* azimuth, void* inclination, void* rgb, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DTI relative-error table -- `calc_diff_maps` + `calc_error_table` / `do_calc_error_avg`
+ * (src/eval.py:154-192, 217-317): predicted and true tensors -> 12 relative-error maps -> their
+ * means over the brain mask weighted by `nroi` (1..4; the reference's 3 = CSF, GM, WM) tissue
+ * probability maps.  Columns: dxx dxy dxz dyy dyz dzz md fa ad rd azimuth inclination.
+ *   tensor components: |p - t| / t of the tensors as passed; md/fa/ad/rd: the same of the scalar maps
+ *   of mi355_dti_scalar_maps (f64) computed after x*scale + offset (pass (1, 0) for none);
+ *   angles: r = (p - t) mod 360 (Python's float remainder), min(r, 360 - r).
+ *   Then |diff|, 0 where mask[v] == 0, +inf -> 0; NaN stays NaN (a 0/0 inside the mask makes that
+ *   column NaN in every ROI, as in the reference).  Weight w_r = probseg_r where mask > 0 and
+ *   probseg_r > 1e-5, else 0; table_out[r*12 + c] = sum w_r diff_c / sum w_r (0/0 = NaN).
+ * pred, target: `dtype` (F32 / F64), component c of voxel v at [v*vox_stride + c*comp_stride]
+ * (NIfTI (X,Y,Z,6): (1, 6); channels-first [6][D][H][W]: (D*H*W, 1)).  mask: uint8 [nvox].
+ * probseg: `probseg_dtype` (F32 / F64, compared and weighted in f64), map r of voxel v at
+ * [v*probseg_vox_stride + r*roi_stride].  workspace: device, >= mi355_dti_errors_workspace_bytes.
+ * table_out: device double[nroi*12].  maps: NULL, or a HOST array of 12 device pointers that receive
+ * the post-processed diff maps ([nvox], `dtype`).  The principal eigenvector keeps the z >= 0 sign
+ * of mi355_dti_scalar_maps: the angle columns equal the reference's where LAPACK's principal
+ * eigenvector also has z > 0.  Sums are f64 in a fixed order: bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int64_t mi355_dti_errors_workspace_bytes(int64_t nvox, int32_t nroi);
+int mi355_dti_errors(const void* pred, const void* target, int32_t dtype, int64_t comp_stride, int64_t vox_stride,
+                     const uint8_t* mask, const void* probseg, int32_t probseg_dtype, int64_t roi_stride,
+                     int64_t probseg_vox_stride, int64_t nvox, int32_t nroi, double scale, double offset,
+                     void* workspace, int64_t workspace_bytes, double* table_out, void* const* maps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sliding-window inference -- the data movement of `predict_step` /
  * `test_step` (src/model.py:291-333) around Generator.forward: TorchIO's GridSampler patch
  * extraction and GridAggregator.add_batch / get_output_tensor (src/data_module.py:168-183).
