@@ -289,7 +289,9 @@ def conv_fwd(x0, x1, wp, coutp, bias, ks, stride, pad, out, grid, os=1, ooff=(0,
         after()
 
 
-WGRAD_PROBE = None      # tests: called as probe(plan kind, desc) before a weight-gradient launch (2 = marching kernel)
+# tests: called as probe(plan kind, desc) before a weight-gradient launch (2 = marching kernel); returns None or a callable that is
+# invoked right after mi355_conv_wgrad (immediate path only: a deferred launch has not reduced into dw yet)
+WGRAD_PROBE = None
 
 
 def conv_wgrad(x0, x1, g, grid, gs, goff, ks, stride, pad, dw, cout, cin, s_co, s_ci, s_k, tbase, tstep,
@@ -331,8 +333,7 @@ def conv_wgrad(x0, x1, g, grid, gs, goff, ks, stride, pad, dw, cout, cin, s_co, 
     need = lib.mi355_conv_wgrad_workspace(C.byref(d))
     if need < 0:
         _lib.check(-1, "conv_wgrad_workspace")
-    if WGRAD_PROBE is not None:
-        WGRAD_PROBE(lib.mi355_conv_wgrad_plan_kind(C.byref(d)), d)
+    after = WGRAD_PROBE(lib.mi355_conv_wgrad_plan_kind(C.byref(d)), d) if WGRAD_PROBE is not None else None
     ws = torch.empty((need // 4,), dtype=torch.float32, device=x0.device)
     d.workspace, d.workspace_bytes = ws.data_ptr(), need
     if defer is not None:
@@ -341,6 +342,8 @@ def conv_wgrad(x0, x1, g, grid, gs, goff, ks, stride, pad, dw, cout, cin, s_co, 
         defer.append((job, ws))
         return
     _lib.check(lib.mi355_conv_wgrad(C.byref(d), _stream()), "conv_wgrad")
+    if after is not None:
+        after()
 
 
 def wgrad_reduce_multi(jobs):
