@@ -530,6 +530,51 @@ int mi355_aug_bias_field(const float* x, float* out, int32_t c, int32_t d, int32
 int mi355_aug_gamma(const float* x, float* out, int64_t count, float gamma, void* stream);
 int mi355_aug_noise(const float* x, float* out, int64_t count, float mean, float std, uint64_t seed, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training patch queue (src/data_module.py:125-188: CropOrPad -> augmentations with keep= ->
+ * UniformSampler -> Queue): ONE launch writes a batch of patches straight from the RAW subject volumes,
+ *     out_j[b][ch][z][y][x] = A_b( P(src_j)[ch][o_b + (z, y, x)] )
+ * P = CropOrPad((td, th, tw), padding_value) with the offsets of augment.crop_or_pad (centred crop, or
+ * (t - n) / 2 pad voxels before; the padded volume is never materialised), o_b = origin of patch b in
+ * padded coordinates, A_b = the stages that fired for the subject load of patch b, in stage[] order, each
+ * bit-identical to the mi355_aug_* call on the padded volume (bias coordinates from the padded shape, noise
+ * keyed by the flat padded (C, D, H, W) index).  An image with augmented[j] == 0 (a kept copy) gets no stage.
+ * All arrays are HOST arrays; they travel by value in the kernel arguments:
+ *   loads[l]                 : stages and parameters of subject load l
+ *   sources[l * nimages + j] : raw (channels[j], d, h, w) f32 volume of image j of load l
+ *   patches[b]               : {load, z, y, x} (origin in padded coordinates)
+ *   outs[j]                  : device [npatches][channels[j]][pd][ph][pw]
+ * A launch takes at most MI355_MAX_PATCHES patches of at most MI355_QUEUE_MAX_LOADS loads; longer lists are
+ * chunked, one launch per chunk.  Rows are read and written 16 bytes per lane wherever alignment allows
+ * (pw % 4 == 0; a source with w % 4 == 0 and a 16-byte aligned base).  No atomics, no host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+#define MI355_QUEUE_MAX_LOADS 4
+#define MI355_QUEUE_MAX_IMAGES 4
+#define MI355_QUEUE_MAX_STAGES 3
+#define MI355_STAGE_BIAS_FIELD 1
+#define MI355_STAGE_NOISE 2
+#define MI355_STAGE_GAMMA 3
+
+typedef struct mi355_queue_load {
+  int32_t nstages;                          /* 0 .. MI355_QUEUE_MAX_STAGES, one stage of each kind at most */
+  int32_t stage[MI355_QUEUE_MAX_STAGES];    /* MI355_STAGE_*, applied in this order */
+  int32_t bias_order;                       /* 0..4 */
+  float bias_coef[35];                      /* (order+1)(order+2)(order+3)/6 used, TorchIO's x-y-z loop order */
+  float noise_mean, noise_std;
+  uint64_t noise_seed;
+  float gamma;
+} mi355_queue_load;
+
+typedef struct mi355_queue_source {
+  const float* src;                         /* device, contiguous (c, d, h, w) f32 */
+  int32_t d, h, w;
+} mi355_queue_source;
+
+int mi355_patch_queue_gather(const mi355_queue_load* loads, int32_t nloads, const mi355_queue_source* sources,
+                             const int32_t* channels, const int32_t* augmented, float* const* outs, int32_t nimages,
+                             const int32_t* patches, int32_t npatches, int32_t td, int32_t th, int32_t tw,
+                             int32_t pd, int32_t ph, int32_t pw, float padding_value, void* stream);
+
 /* layout probe used by the tests: writes lane -> (row, col) maps of the MFMA accumulators */
 int mi355_mfma_selftest(float* out_f32_1024, float* out_bf16_1024, void* stream);
 

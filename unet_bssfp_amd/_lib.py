@@ -68,6 +68,15 @@ class NormActDesc(C.Structure):
                 ("pool_y", _vp), ("ldpy", _i32), ("pool_widx", _vp)]
 
 
+class QueueLoad(C.Structure):
+    _fields_ = [("nstages", _i32), ("stage", _i32 * 3), ("bias_order", _i32), ("bias_coef", _f32 * 35),
+                ("noise_mean", _f32), ("noise_std", _f32), ("noise_seed", _u64), ("gamma", _f32)]
+
+
+class QueueSource(C.Structure):
+    _fields_ = [("src", _vp), ("d", _i32), ("h", _i32), ("w", _i32)]
+
+
 class NormSmallDesc(C.Structure):
     _fields_ = [("base", NormActDesc), ("eps", _f32), ("momentum", _f32), ("mean_out", _vp), ("rstd_out", _vp),
                 ("running_mean", _vp), ("running_var", _vp), ("batches_tracked", _vp), ("n_real", _i32),
@@ -141,6 +150,8 @@ _SIGNATURES = {
     "mi355_aug_bias_field": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "mi355_aug_gamma": (C.c_int, [_vp, _vp, _i64, _f32, _vp]),
     "mi355_aug_noise": (C.c_int, [_vp, _vp, _i64, _f32, _f32, C.c_uint64, _vp]),
+    "mi355_patch_queue_gather": (C.c_int, [C.POINTER(QueueLoad), _i32, C.POINTER(QueueSource), _vp, _vp, _vp, _i32,
+                                           _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "mi355_mfma_selftest": (C.c_int, [_vp, _vp, _vp]),
     "mi355_amax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "mi355_amax_act": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _vp, _vp]),

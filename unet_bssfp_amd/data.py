@@ -1,0 +1,305 @@
+"""Training / validation patch feed on the device -- the reference's ``train_dataloader`` / ``val_dataloader``.
+
+The reference trains through (src/data_module.py:125-188)::
+
+    CropOrPad((96, 128, 128), 0) -> Compose([...augmentations...], keep={'dwi-tensor': 'dwi-tensor_orig'})
+        -> UniformSampler(64) -> Queue(max_length=16, samples_per_volume=8) -> DataLoader(batch_size=8)
+
+Here the subjects stay in HBM as their RAW volumes (uploaded once) and ``PatchQueue.next_batch`` writes a whole batch
+with ONE launch (``mi355_patch_queue_gather``): the crop/pad is index arithmetic, the augmentation stages that fired for
+a patch's subject load run in registers, and the result equals ``extract_patches(chain(crop_or_pad(raw)))`` bit for bit.
+Only the image-space members of the transform are fused (``augment.RandomBiasField``, ``RandomNoise``, ``RandomGamma``);
+any other transform type raises ``TypeError``.
+
+The plan -- which subjects fill the queue, the stages that fire and their parameters, the patch origins and their order
+-- is host logic driven by the queue's own ``torch.Generator`` and needs no GPU (``next_plan``).  TorchIO is absent: the
+structure follows its Queue (fill, shuffle, pop from the end), but its exact random streams are not reproduced
+(**parity unpinned**).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, augment, nifti
+from .inference import DATA, LOCATION, _triple
+
+_STAGE_KIND = {augment.RandomBiasField: 1, augment.RandomNoise: 2, augment.RandomGamma: 3}   # MI355_STAGE_*
+_MAX_IMAGES = 4                                                                              # MI355_QUEUE_MAX_IMAGES
+
+
+def subjects_from_nifti(files: Dict[str, str], device) -> Dict[str, Dict[str, torch.Tensor]]:
+    """One subject ``{name: {'data': (C, D, H, W) f32}}`` from ``{name: path}``, uploaded once.  Like TorchIO's
+    ``ScalarImage``, a 4-D file's last axis becomes the channel axis and a 3-D file gets one channel."""
+    subject = {}
+    for name, path in files.items():
+        arr, _affine = nifti.load(path)
+        if arr.ndim == 3:
+            arr = arr[None]
+        elif arr.ndim == 4:
+            arr = np.moveaxis(arr, -1, 0)
+        else:
+            raise ValueError(f"{path}: expected a 3-D or 4-D image, got shape {arr.shape}")
+        subject[name] = {DATA: torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to(device)}
+    return subject
+
+
+def split_subjects(ids: Sequence, val_split: float = 0.1, test_split: float = 0.1, seed: int = 42):
+    """``random_split(ids, [1 - t - v, v, t], Generator().manual_seed(seed))`` (src/data_module.py:70-75)
+    -> (train, val, test) lists of ids."""
+    ids = list(ids)
+    parts = torch.utils.data.random_split(ids, [1 - test_split - val_split, val_split, test_split],
+                                          torch.Generator().manual_seed(seed))
+    return tuple([ids[i] for i in p.indices] for p in parts)
+
+
+class UniformSampler:
+    """``tio.data.UniformSampler(patch_size)``: every origin uniform in [0, target - patch] per axis (inclusive)."""
+
+    def __init__(self, patch_size):
+        self.patch_size = _triple(patch_size)
+        if min(self.patch_size) <= 0:
+            raise ValueError(f"patch size must be positive, got {self.patch_size}")
+
+    def check(self, spatial_shape: Sequence[int]) -> None:
+        if any(p > s for p, s in zip(self.patch_size, spatial_shape)):
+            raise ValueError(f"Patch size {self.patch_size} cannot be larger than image size {tuple(spatial_shape)}")
+
+    def draw(self, spatial_shape: Sequence[int], n: int, generator: torch.Generator) -> List[Tuple[int, int, int]]:
+        self.check(spatial_shape)
+        axes = [torch.randint(0, s - p + 1, (n,), generator=generator) for s, p in zip(spatial_shape, self.patch_size)]
+        return [tuple(int(a[i]) for a in axes) for i in range(n)]
+
+
+class SubjectLoad(NamedTuple):
+    """One load of a subject into the queue: its position in the list given to the queue, the epoch, the running number
+    of the fill that loaded it, the seed of the global CPU generator under which its stages were drawn, and the stages
+    that fired as (transform, params)."""
+    subject: int
+    epoch: int
+    fill: int
+    seed: int
+    stages: tuple
+
+
+class PlannedPatch(NamedTuple):
+    load: SubjectLoad
+    origin: Tuple[int, int, int]      # first voxel, padded (target_shape) coordinates
+
+
+def _stages_of(transform) -> list:
+    transform = list(transform)
+    seen = set()
+    for t in transform:
+        if type(t) not in _STAGE_KIND:
+            raise TypeError(f"{type(t).__name__} cannot be fused into the patch queue (supported: RandomBiasField, "
+                            "RandomNoise, RandomGamma)")
+        if type(t) in seen:
+            raise TypeError(f"two {type(t).__name__} stages cannot be fused into one patch queue")
+        seen.add(type(t))
+    return transform
+
+
+class PatchQueue:
+    """``tio.Queue(subjects_dataset, max_length, samples_per_volume, sampler)`` over device-resident subjects.
+
+    ``subjects``: list of ``{name: {'data': (C, D, H, W) f32 tensor}}`` at any raw extent; each is cropped / padded to
+    ``target_shape`` (``augment.crop_or_pad``) inside the gather.  A rank reads the shard ``subjects[rank::world]``, each
+    epoch in a fresh permutation.  A fill loads the next ``min(max_length // samples_per_volume, left in the epoch)``
+    subjects; for each load it draws the stages that fire and their parameters, then ``samples_per_volume`` origins;
+    the list is shuffled and patches are popped from the end.  ``len()`` = patches per epoch.
+
+    ``transform``: the augmentations fused into the gather, applied per subject load in list order.  ``None`` (the
+    default) means ``augment.reference_augmentation()``, the reference's training transform; ``[]`` augments nothing.
+    The queue keeps no history: ``last_fill`` holds the loads of the current fill only."""
+
+    def __init__(self, subjects: Sequence[Dict[str, Dict[str, torch.Tensor]]], modality: str, max_length: int = 16,
+                 samples_per_volume: int = 8, sampler: Optional[UniformSampler] = None,
+                 target_shape: Sequence[int] = (96, 128, 128), transform=None,
+                 keep: Optional[Dict[str, str]] = None, seed: int = 0, rank: int = 0, world: int = 1,
+                 padding_value: float = 0.0):
+        self.sampler = UniformSampler(64) if sampler is None else sampler
+        self.target_shape = _triple(target_shape)
+        if min(self.target_shape) <= 0:
+            raise ValueError(f"target shape must be positive, got {self.target_shape}")
+        self.sampler.check(self.target_shape)
+        self.patch_size = self.sampler.patch_size
+        self.transform = _stages_of(augment.reference_augmentation() if transform is None else transform)
+        self.keep = {"dwi-tensor": "dwi-tensor_orig"} if keep is None else dict(keep)
+        if samples_per_volume < 1 or max_length < samples_per_volume:
+            raise ValueError(f"need 1 <= samples_per_volume <= max_length, got {samples_per_volume}, {max_length}")
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"bad rank {rank} of world {world}")
+        self.modality, self.max_length, self.samples_per_volume = modality, int(max_length), int(samples_per_volume)
+        self.padding_value = float(padding_value)
+        everyone = list(subjects)
+        self.indices = list(range(len(everyone)))[rank::world]      # this rank's shard (positions in ``subjects``)
+        self.subjects = [everyone[i] for i in self.indices]
+        self._by_index = dict(zip(self.indices, self.subjects))
+        if not self.subjects:
+            raise ValueError(f"rank {rank} of {world} has no subject")
+        names = [modality] + list(self.keep)
+        self.channels = {}
+        for i, subj in enumerate(self.subjects):
+            for name in names:
+                if name not in subj:
+                    raise ValueError(f"subject {i} of the shard has no image '{name}'")
+                t = subj[name][DATA]
+                if t.dim() != 4:
+                    raise ValueError(f"subject {i} '{name}': expected (C, D, H, W), got {tuple(t.shape)}")
+                if self.channels.setdefault(name, t.shape[0]) != t.shape[0]:
+                    raise ValueError(f"image '{name}' has {t.shape[0]} channels in subject {i}, "
+                                     f"{self.channels[name]} elsewhere")
+        self._gen = torch.Generator().manual_seed(int(seed))
+        self.epoch = -1
+        self._order: List[int] = []          # subjects left in the current epoch (next one at the end)
+        self._patches: List[PlannedPatch] = []
+        self.fill_count = 0                          # fills so far
+        self.last_fill: List[SubjectLoad] = []       # the loads of the current fill, in load order
+
+    def __len__(self):
+        return len(self.subjects) * self.samples_per_volume
+
+    # ---- host plan ---------------------------------------------------------------------------------------------
+    def _draw_stages(self) -> Tuple[int, tuple]:
+        """the stages that fire for one load, drawn like ``_Random.__call__`` (``rand(1) < p``, then ``sample()``)
+        from the global CPU generator seeded from the queue's own generator"""
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=self._gen))
+        stages = []
+        with torch.random.fork_rng(devices=[]):
+            torch.default_generator.manual_seed(seed)
+            for t in self.transform:
+                if torch.rand(1).item() < t.p:
+                    stages.append((t, t.sample()))
+        return seed, tuple(stages)
+
+    def _fill(self) -> None:
+        if not self._order:
+            self.epoch += 1
+            self._order = [self.indices[int(i)] for i in torch.randperm(len(self.indices), generator=self._gen).flip(0)]
+        n = min(self.max_length // self.samples_per_volume, len(self._order))
+        loads, patches = [], []
+        for _ in range(n):
+            seed, stages = self._draw_stages()
+            load = SubjectLoad(self._order.pop(), self.epoch, self.fill_count, seed, stages)
+            loads.append(load)
+            patches += [PlannedPatch(load, o) for o in
+                        self.sampler.draw(self.target_shape, self.samples_per_volume, self._gen)]
+        perm = torch.randperm(len(patches), generator=self._gen)
+        self._patches = [patches[int(i)] for i in perm]
+        self.last_fill = loads
+        self.fill_count += 1
+
+    def next_plan(self, batch_size: int = 8) -> List[PlannedPatch]:
+        """the next ``batch_size`` patches of the queue (host only: no GPU work)"""
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        out = []
+        for _ in range(batch_size):
+            if not self._patches:
+                self._fill()
+            out.append(self._patches.pop())
+        return out
+
+    # ---- device gather -----------------------------------------------------------------------------------------
+    def _images(self, augmented_target: bool):
+        """(output name, source name, augmented) of every image a batch writes"""
+        imgs = [(self.modality, self.modality, True)]
+        for src, kept in self.keep.items():
+            imgs.append((kept, src, False))
+            if augmented_target and src != self.modality:
+                imgs.append((src, src, True))
+        if len(imgs) > _MAX_IMAGES:
+            raise ValueError(f"a batch writes at most {_MAX_IMAGES} images, asked for {[i[0] for i in imgs]}")
+        return imgs
+
+    def _outputs(self, imgs, b: int, out, device):
+        shapes = {name: (b, self.channels[src]) + self.patch_size for name, src, _ in imgs}
+        if out is None:
+            return {name: torch.empty(s, dtype=torch.float32, device=device) for name, s in shapes.items()}
+        got = {}
+        for name, s in shapes.items():
+            if name not in out or not isinstance(out[name], dict) or DATA not in out[name]:
+                raise ValueError(f"out= has no {{'{name}': {{'data': tensor}}}}")
+            t = out[name][DATA]
+            if tuple(t.shape) != s or t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
+                raise ValueError(f"out['{name}']: need a contiguous float32 {s} tensor on {device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device}")
+            got[name] = t
+        spans = sorted((t.data_ptr(), t.data_ptr() + t.numel() * 4, name) for name, t in got.items())
+        for (_, end, a), (start, _, bname) in zip(spans, spans[1:]):
+            if start < end:
+                raise ValueError(f"out['{a}'] and out['{bname}'] share memory: each written image needs its own tensor")
+        return got
+
+    @staticmethod
+    def _load_struct(load: SubjectLoad) -> _lib.QueueLoad:
+        q = _lib.QueueLoad()
+        q.nstages = len(load.stages)
+        for s, (t, params) in enumerate(load.stages):
+            q.stage[s] = _STAGE_KIND[type(t)]
+            if isinstance(t, augment.RandomBiasField):
+                coef = np.asarray(params, dtype=np.float32)
+                q.bias_order = t.order
+                for i, c in enumerate(coef):
+                    q.bias_coef[i] = float(c)
+            elif isinstance(t, augment.RandomNoise):
+                q.noise_mean, q.noise_std, q.noise_seed = float(params[0]), float(params[1]), int(params[2])
+            else:
+                q.gamma = float(params)
+        return q
+
+    def gather(self, plan: Sequence[PlannedPatch], out=None, augmented_target: bool = False):
+        """write the patches of ``plan`` (one launch, or one per chunk of MI355_MAX_PATCHES patches / 4 loads)"""
+        imgs = self._images(augmented_target)
+        sources = {name: [self._by_index[p.load.subject][name][DATA] for p in plan] for _, name, _ in imgs}
+        device = self._by_index[plan[0].load.subject][self.modality][DATA].device
+        for name, ts in sources.items():
+            for t in ts:
+                if not t.is_cuda:
+                    raise _lib.Mi355Error("the patch queue gathers on the GPU only (no CPU fallback)")
+                if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError(f"subject image '{name}' must be a contiguous float32 tensor on {device}")
+        outs = self._outputs(imgs, len(plan), out, device)
+        slot: Dict[int, int] = {}
+        loads: List[SubjectLoad] = []
+        for p in plan:
+            if id(p.load) not in slot:
+                slot[id(p.load)] = len(loads)
+                loads.append(p.load)
+        nimg = len(imgs)
+        qloads = (_lib.QueueLoad * len(loads))(*[self._load_struct(l) for l in loads])
+        qsrc = (_lib.QueueSource * (len(loads) * nimg))()
+        for li, load in enumerate(loads):
+            for j, (_, src, _) in enumerate(imgs):
+                t = self._by_index[load.subject][src][DATA]
+                qsrc[li * nimg + j] = _lib.QueueSource(t.data_ptr(), *t.shape[1:])
+        channels = (C.c_int32 * nimg)(*[self.channels[src] for _, src, _ in imgs])
+        augmented = (C.c_int32 * nimg)(*[int(a) for _, _, a in imgs])
+        ptrs = (C.c_void_p * nimg)(*[outs[name].data_ptr() for name, _, _ in imgs])
+        pat = np.array([[slot[id(p.load)], *p.origin] for p in plan], dtype=np.int32)
+        _lib.check(_lib.load().mi355_patch_queue_gather(
+            qloads, len(loads), qsrc, channels, augmented, ptrs, nimg, pat.ctypes.data_as(C.c_void_p), len(plan),
+            *self.target_shape, *self.patch_size, self.padding_value, torch.cuda.current_stream(device).cuda_stream),
+            "patch_queue_gather")
+        batch = {name: {DATA: outs[name]} for name, _, _ in imgs}
+        ini = np.array([p.origin for p in plan], dtype=np.int64)
+        batch[LOCATION] = torch.from_numpy(np.hstack([ini, ini + np.array(self.patch_size, dtype=np.int64)]))
+        return batch
+
+    def next_batch(self, batch_size: int = 8, out=None, augmented_target: bool = False):
+        """``{modality: {'data'}, <kept>: {'data'}, 'location': (B, 6) int64}`` -- the layout ``unpack_batch`` reads;
+        the augmented ``'dwi-tensor'`` too with ``augmented_target=True``.  With ``out=`` (e.g. the static batch of a
+        ``GraphedTrainingStep``) the launch writes into those tensors: nothing is allocated or copied."""
+        return self.gather(self.next_plan(batch_size), out=out, augmented_target=augmented_target)
+
+    def batches(self, batch_size: int = 8, **kw):
+        """one epoch's worth, like ``DataLoader(queue, batch_size)``: ceil(len / batch_size) batches"""
+        left = len(self)
+        while left > 0:
+            n = min(batch_size, left)
+            left -= n
+            yield self.next_batch(n, **kw)
