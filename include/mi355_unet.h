@@ -575,6 +575,40 @@ int mi355_patch_queue_gather(const mi355_queue_load* loads, int32_t nloads, cons
                              const int32_t* patches, int32_t npatches, int32_t td, int32_t th, int32_t tw,
                              int32_t pd, int32_t ph, int32_t pw, float padding_value, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * k-space and blur augmentations (tio.RandomGhosting, tio.RandomSpike, tio.RandomBlur) without an FFT: one small dense
+ * matrix applied along one axis of a contiguous f32 (C, D, H, W) tensor (axis 0 = D, 1 = H, 2 = W), out of place,
+ *     out[c][..i..] = sum_j M[i][j] * x[c][..j..],   M row-major [N][N] f32 in DEVICE memory.
+ * The extent N along the axis is at most MI355_AXIS_MAX_N; a larger one returns MI355_ERR_UNSUPPORTED (it is not tiled).
+ * Sums run in f32 over j in order, one fma per term.
+ *   mi355_axis_apply             : real M, real x.
+ *   mi355_axis_apply_complex     : complex M (planes mr, mi), real (xi == NULL) or complex (planes xr, xi) input, complex
+ *                                  output as two planes.  The forward DFT runs W (real input), then H, then D; a complex
+ *                                  input along W is correct but slow (one line per workgroup).
+ *   mi355_axis_apply_complex_max : the last DFT pass, along D: writes no volume; out[c] = (max Re, |Im| at the arg-max),
+ *                                  the lexicographic maximum of (Re, |Im|) over the channel's spectrum, as two doubles.
+ *   mi355_channel_sum_min        : out[c] = (sum, min) of channel c, accumulated in f64.
+ *   mi355_aug_spike_add          : out = x + (ar cos(phi) - ai sin(phi)) / (D H W),
+ *                                  phi = 2 pi (f0 n0 / D + f1 n1 / H + f2 n2 / W), (ar, ai) = m[c] * intensity with m[c] two
+ *                                  doubles in DEVICE memory (what the two calls above write); dc != 0 ignores m[c][1]
+ *                                  (m = (sum, min): the spectrum's maximum of a non-negative channel is its DC bin).
+ *                                  The phase is reduced exactly in integers before the f32 sincos.  In-place allowed.
+ * workspace: mi355_kspace_workspace_bytes(c, d, h, w) bytes of device memory, overwritten.  No atomics, no allocation.
+ * ---------------------------------------------------------------------------------------- */
+#define MI355_AXIS_MAX_N 128
+#define MI355_KSPACE_SUM_BLOCKS 128
+int mi355_axis_apply(const float* x, const float* m, float* out, int32_t c, int32_t d, int32_t h, int32_t w,
+                     int32_t axis, void* stream);
+int mi355_axis_apply_complex(const float* xr, const float* xi, const float* mr, const float* mi, float* outr, float* outi,
+                             int32_t c, int32_t d, int32_t h, int32_t w, int32_t axis, void* stream);
+int64_t mi355_kspace_workspace_bytes(int32_t c, int32_t d, int32_t h, int32_t w);
+int mi355_axis_apply_complex_max(const float* xr, const float* xi, const float* mr, const float* mi, int32_t c, int32_t d,
+                                 int32_t h, int32_t w, void* workspace, int64_t workspace_bytes, double* out, void* stream);
+int mi355_channel_sum_min(const float* x, int32_t c, int64_t vol, void* workspace, int64_t workspace_bytes, double* out,
+                          void* stream);
+int mi355_aug_spike_add(const float* x, float* out, int32_t c, int32_t d, int32_t h, int32_t w, int32_t f0, int32_t f1,
+                        int32_t f2, const double* m, int32_t dc, float intensity, void* stream);
+
 /* layout probe used by the tests: writes lane -> (row, col) maps of the MFMA accumulators */
 int mi355_mfma_selftest(float* out_f32_1024, float* out_bf16_1024, void* stream);
 

@@ -152,6 +152,12 @@ _SIGNATURES = {
     "mi355_aug_noise": (C.c_int, [_vp, _vp, _i64, _f32, _f32, C.c_uint64, _vp]),
     "mi355_patch_queue_gather": (C.c_int, [C.POINTER(QueueLoad), _i32, C.POINTER(QueueSource), _vp, _vp, _vp, _i32,
                                            _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "mi355_axis_apply": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mi355_axis_apply_complex": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mi355_kspace_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "mi355_axis_apply_complex_max": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "mi355_channel_sum_min": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _vp]),
+    "mi355_aug_spike_add": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _f32, _vp]),
     "mi355_mfma_selftest": (C.c_int, [_vp, _vp, _vp]),
     "mi355_amax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "mi355_amax_act": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _vp, _vp]),

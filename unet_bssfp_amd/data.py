@@ -8,8 +8,12 @@ The reference trains through (src/data_module.py:125-188)::
 Here the subjects stay in HBM as their RAW volumes (uploaded once) and ``PatchQueue.next_batch`` writes a whole batch
 with ONE launch (``mi355_patch_queue_gather``): the crop/pad is index arithmetic, the augmentation stages that fired for
 a patch's subject load run in registers, and the result equals ``extract_patches(chain(crop_or_pad(raw)))`` bit for bit.
-Only the image-space members of the transform are fused (``augment.RandomBiasField``, ``RandomNoise``, ``RandomGamma``);
-any other transform type raises ``TypeError``.
+The image-space members of the transform are fused (``augment.RandomBiasField``, ``RandomNoise``, ``RandomGamma``).  The
+non-local members (``augment.RandomGhosting``, ``RandomSpike``, ``RandomBlur``) cannot run in the registers of a gather:
+for a load in which one of them fired with an effect, the queue materialises ``chain(crop_or_pad(raw))`` up to and
+including the LAST such stage once, with the stand-alone kernels, into a staging tensor of the target extent; the gather
+reads that tensor as the load's source and fuses only the local stages that follow.  A staged tensor lives no longer than
+the patches of its load.  Any other transform type raises ``TypeError``.
 
 The plan -- which subjects fill the queue, the stages that fire and their parameters, the patch origins and their order
 -- is host logic driven by the queue's own ``torch.Generator`` and needs no GPU (``next_plan``).  TorchIO is absent: the
@@ -28,6 +32,8 @@ from . import _lib, augment, nifti
 from .inference import DATA, LOCATION, _triple
 
 _STAGE_KIND = {augment.RandomBiasField: 1, augment.RandomNoise: 2, augment.RandomGamma: 3}   # MI355_STAGE_*
+_NONLOCAL = (augment.RandomGhosting, augment.RandomSpike, augment.RandomBlur)               # staged, never fused
+_SIGN_PRESERVING = (augment.RandomBiasField, augment.RandomGamma, augment.RandomBlur)      # x >= 0 stays >= 0
 _MAX_IMAGES = 4                                                                              # MI355_QUEUE_MAX_IMAGES
 
 
@@ -94,9 +100,9 @@ def _stages_of(transform) -> list:
     transform = list(transform)
     seen = set()
     for t in transform:
-        if type(t) not in _STAGE_KIND:
+        if type(t) not in _STAGE_KIND and type(t) not in _NONLOCAL:
             raise TypeError(f"{type(t).__name__} cannot be fused into the patch queue (supported: RandomBiasField, "
-                            "RandomNoise, RandomGamma)")
+                            "RandomNoise, RandomGamma, and staged: RandomGhosting, RandomSpike, RandomBlur)")
         if type(t) in seen:
             raise TypeError(f"two {type(t).__name__} stages cannot be fused into one patch queue")
         seen.add(type(t))
@@ -112,7 +118,7 @@ class PatchQueue:
     subjects; for each load it draws the stages that fire and their parameters, then ``samples_per_volume`` origins;
     the list is shuffled and patches are popped from the end.  ``len()`` = patches per epoch.
 
-    ``transform``: the augmentations fused into the gather, applied per subject load in list order.  ``None`` (the
+    ``transform``: the augmentations applied per subject load in list order, fused into the gather or staged before it.  ``None`` (the
     default) means ``augment.reference_augmentation()``, the reference's training transform; ``[]`` augments nothing.
     The queue keeps no history: ``last_fill`` holds the loads of the current fill only."""
 
@@ -153,6 +159,19 @@ class PatchQueue:
                 if self.channels.setdefault(name, t.shape[0]) != t.shape[0]:
                     raise ValueError(f"image '{name}' has {t.shape[0]} channels in subject {i}, "
                                      f"{self.channels[name]} elsewhere")
+        # RandomSpike takes its DC shortcut (M = sum(x)) only where no voxel can be negative; that is decided statically,
+        # from the raw minima read once here, so that next_batch never waits for the device
+        self.nonnegative: Dict[int, bool] = {}
+        if any(type(t) is augment.RandomSpike for t in self.transform):
+            for idx, subj in self._by_index.items():
+                ok = True
+                for name in names:
+                    t = subj[name][DATA]
+                    pads = any(n < g for n, g in zip(t.shape[1:], self.target_shape))
+                    ok = ok and float(t.min()) >= 0 and (self.padding_value >= 0 or not pads)
+                self.nonnegative[idx] = ok
+        self._check_nonlocal()
+        self._staged: Dict[int, Tuple[SubjectLoad, Dict[str, torch.Tensor]]] = {}   # id(load) -> (load, {image: tensor})
         self._gen = torch.Generator().manual_seed(int(seed))
         self.epoch = -1
         self._order: List[int] = []          # subjects left in the current epoch (next one at the end)
@@ -163,17 +182,48 @@ class PatchQueue:
     def __len__(self):
         return len(self.subjects) * self.samples_per_volume
 
+    def _check_nonlocal(self) -> None:
+        """what a staged stage cannot do is refused here, not at the first load in which the stage happens to fire"""
+        limit = augment.AXIS_MAX_N
+        for i, t in enumerate(self.transform):
+            if type(t) is augment.RandomGhosting:
+                axes, what = t.axes, "RandomGhosting"
+            elif type(t) is augment.RandomBlur:
+                axes, what = ((0, 1, 2) if augment.blur_radius(t.std_range[1]) > 0 else ()), "RandomBlur"
+            elif type(t) is augment.RandomSpike:
+                if t.num_spikes_range[1] > 1:
+                    raise ValueError(f"RandomSpike(num_spikes={t.num_spikes_range}): more than one spike per load is not "
+                                     "built on the device")
+                dc_always = all(self.nonnegative.values()) and all(type(b) in _SIGN_PRESERVING for b in self.transform[:i])
+                axes, what = (() if dc_always else (0, 1, 2)), "RandomSpike (DFT path)"
+            else:
+                continue
+            for a in axes:
+                if self.target_shape[a] > limit:
+                    raise ValueError(f"{what} works along axis {a}, where the target extent {self.target_shape[a]} exceeds "
+                                     f"{limit} (larger extents are not tiled)")
+
     # ---- host plan ---------------------------------------------------------------------------------------------
-    def _draw_stages(self) -> Tuple[int, tuple]:
+    def spike_path(self, subject: int, before: Sequence) -> str:
+        """'dc' or 'dft' for a RandomSpike of a load of ``subject`` that runs after the stages ``before`` ((transform,
+        params) pairs that fired): 'dc' only if every image of the subject is non-negative after crop/pad and every
+        earlier stage keeps it so (bias field, gamma, blur); after ghosting or noise, 'dft'"""
+        ok = self.nonnegative.get(subject, False) and all(type(t) in _SIGN_PRESERVING for t, _ in before)
+        return "dc" if ok else "dft"
+
+    def _draw_stages(self, subject: int) -> Tuple[int, tuple]:
         """the stages that fire for one load, drawn like ``_Random.__call__`` (``rand(1) < p``, then ``sample()``)
-        from the global CPU generator seeded from the queue's own generator"""
+        from the global CPU generator seeded from the queue's own generator; a spike's parameters get its path"""
         seed = int(torch.randint(0, 2 ** 62, (1,), generator=self._gen))
         stages = []
         with torch.random.fork_rng(devices=[]):
             torch.default_generator.manual_seed(seed)
             for t in self.transform:
                 if torch.rand(1).item() < t.p:
-                    stages.append((t, t.sample()))
+                    params = t.sample()
+                    if type(t) is augment.RandomSpike:
+                        params = params._replace(path=self.spike_path(subject, stages))
+                    stages.append((t, params))
         return seed, tuple(stages)
 
     def _fill(self) -> None:
@@ -183,8 +233,9 @@ class PatchQueue:
         n = min(self.max_length // self.samples_per_volume, len(self._order))
         loads, patches = [], []
         for _ in range(n):
-            seed, stages = self._draw_stages()
-            load = SubjectLoad(self._order.pop(), self.epoch, self.fill_count, seed, stages)
+            subject = self._order.pop()
+            seed, stages = self._draw_stages(subject)
+            load = SubjectLoad(subject, self.epoch, self.fill_count, seed, stages)
             loads.append(load)
             patches += [PlannedPatch(load, o) for o in
                         self.sampler.draw(self.target_shape, self.samples_per_volume, self._gen)]
@@ -236,10 +287,37 @@ class PatchQueue:
         return got
 
     @staticmethod
-    def _load_struct(load: SubjectLoad) -> _lib.QueueLoad:
+    def split_stages(load: SubjectLoad) -> Tuple[tuple, tuple]:
+        """(staged, fused): the stages up to and including the last non-local one that has an effect, applied once
+        into a staging tensor, and the local stages after it, fused into the gather.  A non-local stage without an
+        effect (a blur whose three radii are 0, a ghosting or spike of intensity 0) is the identity and is dropped."""
+        live = [(t, p) for t, p in load.stages if type(t) not in _NONLOCAL or t.has_effect(p)]
+        last = max((i for i, (t, _) in enumerate(live) if type(t) in _NONLOCAL), default=-1)
+        return tuple(live[:last + 1]), tuple(live[last + 1:])
+
+    def _staged_source(self, load: SubjectLoad, staged: tuple, name: str) -> torch.Tensor:
+        """chain(crop_or_pad(raw)) through ``staged`` for one image of one load, made once and kept while the load has
+        patches"""
+        entry = self._staged.setdefault(id(load), (load, {}))[1]
+        if name not in entry:
+            x = augment.crop_or_pad(self._by_index[load.subject][name][DATA], self.target_shape, self.padding_value)
+            for t, params in staged:
+                x = t.apply(x, params)
+            entry[name] = x
+        return entry[name]
+
+    def _release_staged(self, plan: Sequence[PlannedPatch]) -> None:
+        """drop the staging tensors of loads that have no patch left, in this batch or in the queue"""
+        if self._staged:
+            live = {id(p.load) for p in plan} | {id(p.load) for p in self._patches}
+            for key in [k for k in self._staged if k not in live]:
+                del self._staged[key]
+
+    @staticmethod
+    def _load_struct(stages: tuple) -> _lib.QueueLoad:
         q = _lib.QueueLoad()
-        q.nstages = len(load.stages)
-        for s, (t, params) in enumerate(load.stages):
+        q.nstages = len(stages)
+        for s, (t, params) in enumerate(stages):
             q.stage[s] = _STAGE_KIND[type(t)]
             if isinstance(t, augment.RandomBiasField):
                 coef = np.asarray(params, dtype=np.float32)
@@ -271,11 +349,15 @@ class PatchQueue:
                 slot[id(p.load)] = len(loads)
                 loads.append(p.load)
         nimg = len(imgs)
-        qloads = (_lib.QueueLoad * len(loads))(*[self._load_struct(l) for l in loads])
+        self._release_staged(plan)
+        split = [self.split_stages(l) for l in loads]
+        qloads = (_lib.QueueLoad * len(loads))(*[self._load_struct(fused) for _, fused in split])
         qsrc = (_lib.QueueSource * (len(loads) * nimg))()
         for li, load in enumerate(loads):
-            for j, (_, src, _) in enumerate(imgs):
+            for j, (_, src, aug) in enumerate(imgs):
                 t = self._by_index[load.subject][src][DATA]
+                if aug and split[li][0]:          # a source of the target extent: the gather's crop/pad is the identity
+                    t = self._staged_source(load, split[li][0], src)
                 qsrc[li * nimg + j] = _lib.QueueSource(t.data_ptr(), *t.shape[1:])
         channels = (C.c_int32 * nimg)(*[self.channels[src] for _, src, _ in imgs])
         augmented = (C.c_int32 * nimg)(*[int(a) for _, _, a in imgs])
