@@ -609,6 +609,28 @@ int mi355_channel_sum_min(const float* x, int32_t c, int64_t vol, void* workspac
 int mi355_aug_spike_add(const float* x, float* out, int32_t c, int32_t d, int32_t h, int32_t w, int32_t f0, int32_t f1,
                         int32_t f2, const double* m, int32_t dc, float intensity, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rigid trilinear resampling and tio.RandomMotion on a contiguous f32 (C, D, H, W) tensor, out of place.
+ * A transform is the first three rows of an index-space matrix, row-major float[12] in HOST memory: output voxel
+ * i = (i_D, i_H, i_W) reads the input at s_a = m[4a] i_D + m[4a+1] i_H + m[4a+2] i_W + m[4a+3] (three fmas per axis in
+ * f32).  Inside iff -0.5 <= s_a < N_a - 0.5 on every axis: trilinear between floor(s) and floor(s) + 1, both clamped into
+ * [0, N_a - 1].  Outside: the fill value.
+ *   mi355_rigid_resample : one transform, writes a volume.  channel_min != NULL: DEVICE memory, two doubles per channel as
+ *                          mi355_channel_sum_min writes them; the fill value of channel c is its minimum channel_min[2c+1]
+ *                          and `fill` is ignored.  NULL: every channel is filled with `fill`.
+ *   mi355_aug_motion     : out = sum_k C_k resample(x, m_k), k < nimg, C_k = band_matrices[k] a row-major [Wpad][W] f32
+ *                          matrix in DEVICE memory applied along W, Wpad = W rounded up to a multiple of 8, the rows
+ *                          W..Wpad-1 zero (they are read, their sums are dropped); band_matrices is not written during the
+ *                          launch.  The fill value is the channel minimum (channel_min as above, not NULL).  The resampled copies live in LDS only.  Sums run image by image, j in order, one fma per
+ *                          term.  nimg <= MI355_MOTION_MAX_IMAGES and W <= MI355_AXIS_MAX_N, else MI355_ERR_UNSUPPORTED.
+ * No atomics, no workspace, no host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+#define MI355_MOTION_MAX_IMAGES 8
+int mi355_rigid_resample(const float* x, float* out, int32_t c, int32_t d, int32_t h, int32_t w, const float* m,
+                         const double* channel_min, float fill, void* stream);
+int mi355_aug_motion(const float* x, float* out, int32_t c, int32_t d, int32_t h, int32_t w, int32_t nimg, const float* m,
+                     const float* band_matrices, const double* channel_min, void* stream);
+
 /* layout probe used by the tests: writes lane -> (row, col) maps of the MFMA accumulators */
 int mi355_mfma_selftest(float* out_f32_1024, float* out_bf16_1024, void* stream);
 

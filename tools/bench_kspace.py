@@ -128,18 +128,23 @@ def forced_six():
     return tr
 
 
-def queue_lines(res, subs):
+def queue_lines(res, subs, sets=None):
+    """``sets``: (name, transform, batches) per line; the default compares the three-stage and the six-stage transform"""
     out = {"bssfp": {"data": torch.empty(8, 24, 64, 64, 64, device=DEV)},
            "dwi-tensor_orig": {"data": torch.empty(8, 6, 64, 64, 64, device=DEV)}}
-    for name, tr, iters in (("three_stage_p0.1", A.reference_augmentation(), 400),
-                            ("six_stage_p0.1", A.reference_training_transform(), 400),     # 400 batches = 200 fills
-                            ("six_stage_forced", forced_six(), 40)):
+    if sets is None:
+        sets = (("three_stage_p0.1", A.reference_augmentation(), 400),
+                ("six_stage_p0.1", A.reference_training_transform(), 400),     # 400 batches = 200 fills
+                ("six_stage_forced", forced_six(), 40))
+    for name, tr, iters in sets:
         q = Q.PatchQueue(subs, "bssfp", transform=tr, seed=0)
         note(res, f"queue_{name}_ms_per_batch", round(timed(lambda: q.next_batch(8, out=out), iters=iters, warmup=4), 4))
         note(res, f"queue_{name}_fills", q.fill_count)
 
 
-def step_lines(res, subs, blocks=6, per_block=20):
+def step_lines(res, subs, feeds=None, blocks=6, per_block=20):
+    """``feeds``: {name: transform, or None for the static batch}, in the order in which each is compared with the one
+    before it; the default is static, three-stage, six-stage"""
     import unet_bssfp_amd as M
     from unet_bssfp_amd.gan import GraphedTrainingStep, bSSFPToDWITensorModel, synthetic_batch
     torch.manual_seed(0)
@@ -147,27 +152,30 @@ def step_lines(res, subs, blocks=6, per_block=20):
     M.set_compute_dtype(model, M.compute_dtype_from_name("bf16"))
     gstep = GraphedTrainingStep(model, synthetic_batch(8, 64, seed=1234, device=DEV), warmup=2)
     static = gstep.instances[0][0]
-    q3 = Q.PatchQueue(subs, "bssfp", transform=A.reference_augmentation(), seed=0)
-    q6 = Q.PatchQueue(subs, "bssfp", transform=A.reference_training_transform(), seed=0)
+    if feeds is None:
+        feeds = {"static": None, "three": A.reference_augmentation(), "six": A.reference_training_transform()}
+    queues = {k: Q.PatchQueue(subs, "bssfp", transform=tr, seed=0) for k, tr in feeds.items() if tr is not None}
 
     def fed(q):
         q.next_batch(8, out=static)
         gstep()
     for _ in range(10):
-        fed(q3), fed(q6)
+        for q in queues.values():
+            fed(q)
     torch.cuda.synchronize()
-    runs = {"static": gstep, "three": lambda: fed(q3), "six": lambda: fed(q6)}
+    runs = {k: (lambda q=queues[k]: fed(q)) if k in queues else gstep for k in feeds}
     ms = {k: [] for k in runs}
     names = list(runs)
     for blk in range(blocks):
-        for name in names[blk % 3:] + names[:blk % 3]:
+        r = blk % len(names)
+        for name in names[r:] + names[:r]:
             ms[name].append(timed(runs[name], iters=per_block, warmup=2))
     med = {k: float(np.median(v)) for k, v in ms.items()}
     logs = torch.stack([v.reshape(()).float() for v in model.last_logs.values()])
     res["step_8x64_ms"] = {k: round(v, 3) for k, v in med.items()}
     res["step_blocks_ms"] = {k: [round(v, 3) for v in vs] for k, vs in ms.items()}
-    res["step_three_over_static"] = round(med["three"] / med["static"], 4)
-    res["step_six_over_three"] = round(med["six"] / med["three"], 4)
+    for a, b in zip(names, names[1:]):
+        res[f"step_{b}_over_{a}"] = round(med[b] / med[a], 4)
     res["step_logs_finite"] = bool(torch.isfinite(logs).all())
 
 

@@ -158,6 +158,8 @@ _SIGNATURES = {
     "mi355_axis_apply_complex_max": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "mi355_channel_sum_min": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _vp]),
     "mi355_aug_spike_add": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _f32, _vp]),
+    "mi355_rigid_resample": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp]),
+    "mi355_aug_motion": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mi355_mfma_selftest": (C.c_int, [_vp, _vp, _vp]),
     "mi355_amax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "mi355_amax_act": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _vp, _vp]),

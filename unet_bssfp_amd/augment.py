@@ -12,10 +12,16 @@ dense matrix applied along one axis of the volume (``axis_apply``, csrc/kspace.h
 reading of TorchIO 0.19.6 and are normative here; parity with TorchIO itself is **unpinned** like the rest.  The matrix
 builders (``ghosting_matrix``, ``blur_matrix``, ``dft_matrix``, ``spike_frequencies``, ``spike_closed_form``) are plain
 f64 host functions; a matrix is rounded to f32 once, when it is uploaded.  Blur takes the voxel spacing as 1 (the
-project's subjects carry no affine).  Only RandomMotion (a rigid resampler) is not built.
+project's subjects carry no affine).
+
+``RandomMotion``, the first stage of the reference's list, needs no FFT either: the band composite of
+the K + 1 moved copies is ``sum_k C_k x_k`` with real circulants along the last axis, and one launch fuses the rigid
+trilinear resampler (``rigid_resample`` on its own) with that sum (csrc/motion.hip).  ``reference_full_transform()``
+lists all seven stages.
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -43,6 +49,8 @@ def _check(x: torch.Tensor):
 
 
 class _Random:
+    per_image = False       # one parameter set per call for every image of the subject (RandomMotion: one per image)
+
     def __init__(self, p: float = 1.0):
         self.p = float(p)
 
@@ -217,6 +225,118 @@ def spike_closed_form(x: np.ndarray, positions, intensity: float):
         amps.append(a)
         y += (a.real * cs - a.imag * sn) / x.size
     return y, amps
+
+
+# ---- motion: host mathematics (f64) ------------------------------------------------------------------------------------
+
+def _hat(v: np.ndarray) -> np.ndarray:
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def _se3_log(m: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """the principal logarithm of a rigid 4 x 4 matrix in closed form: (omega, v) with ``logm(M) = [[hat(omega), v], [0, 0]]``,
+    ``v = V^-1 t``.  The unit axis k = omega / theta keeps every coefficient free of a division by theta^2; the identity and
+    pure translations (theta = 0: not diagonalisable) take the first-order branch, which is exact to theta^2."""
+    r, t = m[:3, :3], m[:3, 3]
+    s = 0.5 * np.array([r[2, 1] - r[1, 2], r[0, 2] - r[2, 0], r[1, 0] - r[0, 1]])     # sin(theta) k
+    sin_t, cos_t = float(np.linalg.norm(s)), 0.5 * (float(np.trace(r)) - 1.0)
+    if cos_t < -0.99:
+        raise ValueError("a rotation within 8 degrees of a half turn has no stable principal logarithm")
+    theta = math.atan2(sin_t, cos_t)
+    if theta < 1e-8:
+        return s, t - 0.5 * np.cross(s, t)
+    k = _hat(s / sin_t)
+    half = 0.5 * theta
+    v_inv = np.eye(3) - half * k + (1.0 - half * math.cos(half) / math.sin(half)) * (k @ k)
+    return theta * s / sin_t, v_inv @ t
+
+
+def _se3_exp(omega: np.ndarray, v: np.ndarray) -> np.ndarray:
+    """``expm([[hat(omega), v], [0, 0]])`` in closed form (Rodrigues; ``t = V v``)"""
+    theta = float(np.linalg.norm(omega))
+    out = np.eye(4)
+    if theta < 1e-8:
+        out[:3, :3] += _hat(omega)
+        out[:3, 3] = v + 0.5 * np.cross(omega, v)
+        return out
+    k = _hat(omega / theta)
+    kk = k @ k
+    versine = 2.0 * math.sin(0.5 * theta) ** 2                      # 1 - cos(theta) without the cancellation
+    out[:3, :3] += math.sin(theta) * k + versine * kk
+    out[:3, 3] = (np.eye(3) + (versine / theta) * k + (1.0 - math.sin(theta) / theta) * kk) @ v
+    return out
+
+
+def euler_index_matrix(degrees: Sequence[float], translation: Sequence[float], shape: Sequence[int]) -> np.ndarray:
+    """ITK's ``Euler3DTransform`` in index space (spacing 1, physical point = voxel index) as a 4 x 4 f64 matrix:
+    ``p_in = R (p_out - c) + c + t``, ``R = Rz Rx Ry`` (ITK's default order), centre ``c = shape / 2``"""
+    ax, ay, az = (math.radians(float(d)) for d in degrees)
+    cx, sx, cy, sy, cz, sz = math.cos(ax), math.sin(ax), math.cos(ay), math.sin(ay), math.cos(az), math.sin(az)
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]])
+    ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+    rz = np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]])
+    r = rz @ rx @ ry
+    c = 0.5 * np.asarray(shape, dtype=np.float64)
+    m = np.eye(4)
+    m[:3, :3] = r
+    m[:3, 3] = c + np.asarray(translation, dtype=np.float64) - r @ c
+    return m
+
+
+def motion_matrices(degrees, translation, shape: Sequence[int]) -> np.ndarray:
+    """RandomMotion's transforms as (K + 1, 4, 4) f64 index-space matrices (output voxel ``i`` reads the input at
+    ``M i``): the identity and the K Euler draws (``degrees``, ``translation``: (K, 3)), demeaned as TorchIO does,
+    ``mean = expm(mean_k logm(M_k))``, ``M_k <- inv(mean) M_k``.  The logarithm and exponential are the closed SE(3) forms."""
+    degrees = np.asarray(degrees, dtype=np.float64).reshape(-1, 3)
+    translation = np.asarray(translation, dtype=np.float64).reshape(-1, 3)
+    if len(degrees) != len(translation):
+        raise ValueError(f"{len(degrees)} rotations for {len(translation)} translations")
+    ms = [np.eye(4)] + [euler_index_matrix(d, t, shape) for d, t in zip(degrees, translation)]
+    logs = [_se3_log(m) for m in ms]
+    mean = _se3_exp(np.mean([w for w, _ in logs], axis=0), np.mean([v for _, v in logs], axis=0))
+    inv = np.eye(4)
+    inv[:3, :3] = mean[:3, :3].T
+    inv[:3, 3] = -mean[:3, :3].T @ mean[:3, 3]
+    return np.stack([inv @ m for m in ms])
+
+
+def motion_bands(times, n_axis: int) -> list:
+    """which image owns which bins of the shifted spectrum along the last axis: ``[(image, first, last), ...]``, bins
+    ``[first, last)``.  TorchIO: ``idx = (N * times).astype(int)`` with N appended; ``sort_spectra`` swaps image 0 (the
+    identity before demeaning) with image ``j``, ``j`` the first index with ``times[j] > 0.5``, else K, so that it fills
+    the centre of k-space; then the image at position k owns ``[idx[k - 1], idx[k])``.  Empty bands are dropped."""
+    times = np.asarray(times)
+    n, k = int(n_axis), len(times)
+    order = list(range(k + 1))
+    above = np.nonzero(times > 0.5)[0]
+    j = int(above.min()) if len(above) else k
+    order[0], order[j] = order[j], order[0]
+    idx = (n * times).astype(int).tolist() + [n]
+    bands, ini = [], 0
+    for image, fin in zip(order, idx):
+        if fin > ini:
+            bands.append((image, ini, fin))
+        ini = fin
+    return bands
+
+
+@functools.lru_cache(maxsize=8)
+def _cos_phase(n: int) -> np.ndarray:
+    """cos(_phase_matrix(n)), kept per extent: RandomMotion builds K + 1 band matrices per call from it"""
+    c = np.cos(_phase_matrix(n))
+    c.setflags(write=False)
+    return c
+
+
+def motion_band_matrix(n_axis: int, first: int, last: int) -> np.ndarray:
+    """keeping the bins ``[first, last)`` of the shifted spectrum along one axis of a real volume and taking the real part
+    of the inverse, as a real f64 (N, N) circulant ``C[i][j] = g[(i - j) mod N]``, ``g = real(ifft(ifftshift(b)))``"""
+    n = int(n_axis)
+    b = np.zeros(n, dtype=np.float64)
+    b[int(first):int(last)] = 1.0
+    g = _cos_phase(n) @ np.roll(b, -(n // 2)) / n
+    i = np.arange(n)
+    return g[(i[:, None] - i[None, :]) % n]
 
 
 # ---- k-space and blur stages: device side ----------------------------------------------------------------------------
@@ -412,6 +532,131 @@ class RandomBlur(_Random):
         return x
 
 
+MOTION_MAX_IMAGES = 8   # MI355_MOTION_MAX_IMAGES: K + 1 of one fused launch
+
+
+def _rigid_rows(matrix) -> np.ndarray:
+    """the first three rows of a 4 x 4 (or 3 x 4) index-space matrix as 12 f32 (the one rounding)"""
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape not in ((4, 4), (3, 4)):
+        raise ValueError(f"need a 4 x 4 or 3 x 4 matrix, got {m.shape}")
+    return np.ascontiguousarray(m[:3], dtype=np.float32).reshape(12)
+
+
+def rigid_resample(x: torch.Tensor, matrix, fill: Optional[float] = None) -> torch.Tensor:
+    """``sitk.Resample(image, image, transform, sitkLinear, fill)`` on a (C, D, H, W) device tensor with voxel spacing 1:
+    output voxel ``i`` reads the input at the continuous index ``matrix @ (i, 1)``, trilinearly, inside
+    ``-0.5 <= s < N - 0.5``; outside it gets ``fill``, or with ``fill=None`` the minimum of its channel, which is read
+    on the device (no synchronisation)."""
+    x = _check(x)
+    m = _rigid_rows(matrix)
+    cmin = channel_sum_min(x) if fill is None else None
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().mi355_rigid_resample(x.data_ptr(), out.data_ptr(), *x.shape, m.ctypes.data,
+                                                None if cmin is None else cmin.data_ptr(),
+                                                0.0 if fill is None else float(fill), _stream()), "rigid_resample")
+    return out
+
+
+class MotionParams(NamedTuple):
+    """one image's RandomMotion draw: ``times`` (K,) f32 in (0, 1), ``degrees`` and ``translation`` (K, 3) f32"""
+    times: np.ndarray
+    degrees: np.ndarray
+    translation: np.ndarray
+
+
+class RandomMotion(_Random):
+    """``tio.RandomMotion``: the spectra of K + 1 rigidly moved copies of the volume composited in bands along the last
+    spatial axis, real part kept; on the device ``sum_k C_k resample(x, M_k)`` in one launch (``motion_matrices``,
+    ``motion_bands``, ``motion_band_matrix``).  Spatial axes (0, 1, 2) of (C, D, H, W) are x, y, z; voxel
+    spacing is 1 and a physical point is its voxel index (the project's subjects carry no affine).  The LPS sign flip of
+    TorchIO's ``nib_to_sitk`` is not reproduced: with ranges symmetric about 0 it only relabels the draws.  Unlike the
+    other stages, TorchIO draws a fresh parameter set per image of a subject, and so does ``__call__``.  Only linear
+    interpolation is built.  At most 7 transforms per call; the extent along W is at most 128.  The demeaning takes the
+    principal logarithm of every draw, which is unstable within 8 degrees of a half turn (``motion_matrices`` raises
+    there).  A draw's three Euler angles compose to a rotation of at most their sum, so a ``degrees`` range that reaches
+    beyond +-55 is refused at construction instead of failing in the load where such a draw appears."""
+
+    per_image = True
+    MAX_DEGREES = 55.0      # 3 x 55 = 165 < 171.9 = acos(-0.99), the limit of _se3_log
+
+    def __init__(self, degrees: Range = 10, translation: Range = 10, num_transforms: int = 2,
+                 image_interpolation: str = "linear", p: float = 1.0):
+        super().__init__(p)
+        if image_interpolation != "linear":
+            raise NotImplementedError(f"image_interpolation={image_interpolation!r}: only 'linear' is built")
+        if int(num_transforms) < 1:
+            raise ValueError(f"num_transforms must be at least 1, got {num_transforms}")
+        self.degrees_range, self.translation_range = _range(degrees, True), _range(translation, True)
+        if max(abs(v) for v in self.degrees_range) > self.MAX_DEGREES:
+            raise ValueError(f"degrees={degrees}: a range beyond +-{self.MAX_DEGREES:g} can compose to a rotation near a half "
+                             "turn, where the demeaning of the transforms is not built")
+        self.num_transforms, self.image_interpolation = int(num_transforms), image_interpolation
+
+    def sample(self) -> MotionParams:
+        """one image's parameters, drawn in TorchIO's order: degrees, translation, times"""
+        k = self.num_transforms
+        degrees = torch.FloatTensor(k, 3).uniform_(*self.degrees_range)
+        translation = torch.FloatTensor(k, 3).uniform_(*self.translation_range)
+        step = 1 / (k + 1)
+        times = torch.arange(0, 1, step)[1:] + torch.FloatTensor(k).uniform_(-0.3 * step, 0.3 * step)
+        return MotionParams(times.numpy(), degrees.numpy(), translation.numpy())
+
+    @staticmethod
+    def has_effect(params) -> bool:
+        """false iff every rotation and translation is 0 (every copy is the input and the bands sum to the identity);
+        for the per-image dict of a patch-queue load: whether any image's set has an effect"""
+        if isinstance(params, dict):
+            return any(RandomMotion.has_effect(p) for p in params.values())
+        return bool(np.any(np.asarray(params[1]) != 0) or np.any(np.asarray(params[2]) != 0))
+
+    def apply(self, x, params):
+        params = MotionParams(*params)
+        x = _check(x)
+        if not self.has_effect(params):
+            return x
+        n = x.shape[3]
+        if n > AXIS_MAX_N:
+            raise _lib.Mi355Error(f"RandomMotion: extent {n} along axis 2 exceeds {AXIS_MAX_N} (larger extents are not tiled)")
+        if len(params.times) + 1 > MOTION_MAX_IMAGES:
+            raise _lib.Mi355Error(f"RandomMotion: {len(params.times)} transforms per call exceed {MOTION_MAX_IMAGES - 1}")
+        cmin = channel_sum_min(x)                                      # enqueued first: it runs while the host builds matrices
+        ms = motion_matrices(params.degrees, params.translation, x.shape[1:])
+        bands = motion_bands(params.times, n)
+        rows = np.concatenate([_rigid_rows(ms[image]) for image, _, _ in bands])
+        cmat = np.zeros((len(bands), -(-n // 8) * 8, n))               # rows padded to a multiple of 8 with zeros
+        for b, (_, first, last) in enumerate(bands):
+            cmat[b, :n] = motion_band_matrix(n, first, last)
+        cmat = _upload(cmat, x.device)
+        out = torch.empty_like(x)
+        _lib.check(_lib.load().mi355_aug_motion(x.data_ptr(), out.data_ptr(), *x.shape, len(bands), rows.ctypes.data,
+                                                cmat.data_ptr(), cmin.data_ptr(), _stream()), "aug_motion")
+        return out
+
+    def apply_chained(self, x, params):
+        """the same stage as K + 1 stand-alone resamples and K + 1 passes of ``axis_apply``, summed image by image: the
+        comparator of the fused launch (tests, tools/bench_motion.py), not a fallback"""
+        params = MotionParams(*params)
+        x = _check(x)
+        if not self.has_effect(params):
+            return x
+        ms = motion_matrices(params.degrees, params.translation, x.shape[1:])
+        out = None
+        for image, first, last in motion_bands(params.times, x.shape[3]):
+            y = axis_apply(rigid_resample(x, ms[image]), motion_band_matrix(x.shape[3], first, last), 2)
+            out = y if out is None else out + y
+        return out
+
+    def __call__(self, subject):
+        """one decision per call whether the stage fires, then one parameter set per image, in the subject's order"""
+        if torch.rand(1).item() >= self.p:
+            return subject
+        if isinstance(subject, torch.Tensor):
+            return self.apply(subject, self.sample())
+        return {k: ({**v, "data": self.apply(v["data"], self.sample())} if isinstance(v, dict) and "data" in v else v)
+                for k, v in subject.items()}
+
+
 def crop_or_pad(x: torch.Tensor, target: Sequence[int], padding_value: float = 0.0) -> torch.Tensor:
     """``tio.CropOrPad(target, 0)`` (src/data_module.py:125-128): centred crop / constant pad of (C, D, H, W)."""
     out = x
@@ -433,8 +678,13 @@ def reference_augmentation() -> list:
 
 
 def reference_training_transform() -> list:
-    """the reference's training transform, src/data_module.py:131-139, in its order and with its arguments -- the six
-    members that are built.  The seventh, RandomMotion (first in the reference's list), is missing: it needs a rigid
-    resampler."""
+    """the reference's training transform, src/data_module.py:131-139, in its order and with its arguments, without its
+    first member: the six stages from RandomGhosting on.  With RandomMotion in front: ``reference_full_transform()``."""
     return [RandomGhosting(p=0.1), RandomSpike(p=0.1, intensity=(0.01, 0.1)), RandomBiasField(p=0.1),
             RandomBlur(p=0.1, std=(0.01, 0.1)), RandomNoise(p=0.1, std=(0.01, 0.1)), RandomGamma(p=0.1)]
+
+
+def reference_full_transform() -> list:
+    """all seven stages of the reference's training transform, src/data_module.py:131-139, in its order and with its
+    arguments: ``RandomMotion(p=0.1)`` first, then ``reference_training_transform()``"""
+    return [RandomMotion(p=0.1)] + reference_training_transform()

@@ -9,11 +9,12 @@ Here the subjects stay in HBM as their RAW volumes (uploaded once) and ``PatchQu
 with ONE launch (``mi355_patch_queue_gather``): the crop/pad is index arithmetic, the augmentation stages that fired for
 a patch's subject load run in registers, and the result equals ``extract_patches(chain(crop_or_pad(raw)))`` bit for bit.
 The image-space members of the transform are fused (``augment.RandomBiasField``, ``RandomNoise``, ``RandomGamma``).  The
-non-local members (``augment.RandomGhosting``, ``RandomSpike``, ``RandomBlur``) cannot run in the registers of a gather:
-for a load in which one of them fired with an effect, the queue materialises ``chain(crop_or_pad(raw))`` up to and
+non-local members (``augment.RandomMotion``, ``RandomGhosting``, ``RandomSpike``, ``RandomBlur``) cannot run in the
+registers of a gather: for a load in which one of them fired with an effect, the queue materialises ``chain(crop_or_pad(raw))`` up to and
 including the LAST such stage once, with the stand-alone kernels, into a staging tensor of the target extent; the gather
 reads that tensor as the load's source and fuses only the local stages that follow.  A staged tensor lives no longer than
-the patches of its load.  Any other transform type raises ``TypeError``.
+the patches of its load.  ``RandomMotion`` draws one parameter set per augmented image of a load (as TorchIO does per
+image of a subject), the other stages one per load.  Any other transform type raises ``TypeError``.
 
 The plan -- which subjects fill the queue, the stages that fire and their parameters, the patch origins and their order
 -- is host logic driven by the queue's own ``torch.Generator`` and needs no GPU (``next_plan``).  TorchIO is absent: the
@@ -32,7 +33,7 @@ from . import _lib, augment, nifti
 from .inference import DATA, LOCATION, _triple
 
 _STAGE_KIND = {augment.RandomBiasField: 1, augment.RandomNoise: 2, augment.RandomGamma: 3}   # MI355_STAGE_*
-_NONLOCAL = (augment.RandomGhosting, augment.RandomSpike, augment.RandomBlur)               # staged, never fused
+_NONLOCAL = (augment.RandomMotion, augment.RandomGhosting, augment.RandomSpike, augment.RandomBlur)   # staged, never fused
 _SIGN_PRESERVING = (augment.RandomBiasField, augment.RandomGamma, augment.RandomBlur)      # x >= 0 stays >= 0
 _MAX_IMAGES = 4                                                                              # MI355_QUEUE_MAX_IMAGES
 
@@ -83,7 +84,8 @@ class UniformSampler:
 class SubjectLoad(NamedTuple):
     """One load of a subject into the queue: its position in the list given to the queue, the epoch, the running number
     of the fill that loaded it, the seed of the global CPU generator under which its stages were drawn, and the stages
-    that fired as (transform, params)."""
+    that fired as (transform, params); the params of a per-image stage (``RandomMotion``) are ``{image name: params}``
+    for the modality and every kept source."""
     subject: int
     epoch: int
     fill: int
@@ -102,7 +104,7 @@ def _stages_of(transform) -> list:
     for t in transform:
         if type(t) not in _STAGE_KIND and type(t) not in _NONLOCAL:
             raise TypeError(f"{type(t).__name__} cannot be fused into the patch queue (supported: RandomBiasField, "
-                            "RandomNoise, RandomGamma, and staged: RandomGhosting, RandomSpike, RandomBlur)")
+                            "RandomNoise, RandomGamma, and staged: RandomMotion, RandomGhosting, RandomSpike, RandomBlur)")
         if type(t) in seen:
             raise TypeError(f"two {type(t).__name__} stages cannot be fused into one patch queue")
         seen.add(type(t))
@@ -186,7 +188,12 @@ class PatchQueue:
         """what a staged stage cannot do is refused here, not at the first load in which the stage happens to fire"""
         limit = augment.AXIS_MAX_N
         for i, t in enumerate(self.transform):
-            if type(t) is augment.RandomGhosting:
+            if type(t) is augment.RandomMotion:
+                axes, what = (2,), "RandomMotion"
+                if t.num_transforms + 1 > augment.MOTION_MAX_IMAGES:
+                    raise ValueError(f"RandomMotion(num_transforms={t.num_transforms}): more than "
+                                     f"{augment.MOTION_MAX_IMAGES - 1} transforms per image are not built on the device")
+            elif type(t) is augment.RandomGhosting:
                 axes, what = t.axes, "RandomGhosting"
             elif type(t) is augment.RandomBlur:
                 axes, what = ((0, 1, 2) if augment.blur_radius(t.std_range[1]) > 0 else ()), "RandomBlur"
@@ -207,24 +214,33 @@ class PatchQueue:
     def spike_path(self, subject: int, before: Sequence) -> str:
         """'dc' or 'dft' for a RandomSpike of a load of ``subject`` that runs after the stages ``before`` ((transform,
         params) pairs that fired): 'dc' only if every image of the subject is non-negative after crop/pad and every
-        earlier stage keeps it so (bias field, gamma, blur); after ghosting or noise, 'dft'"""
+        earlier stage keeps it so (bias field, gamma, blur); after motion, ghosting or noise, 'dft'"""
         ok = self.nonnegative.get(subject, False) and all(type(t) in _SIGN_PRESERVING for t, _ in before)
         return "dc" if ok else "dft"
 
     def _draw_stages(self, subject: int) -> Tuple[int, tuple]:
         """the stages that fire for one load, drawn like ``_Random.__call__`` (``rand(1) < p``, then ``sample()``)
-        from the global CPU generator seeded from the queue's own generator; a spike's parameters get its path"""
+        from the global CPU generator seeded from the queue's own generator; a spike's parameters get its path.  A
+        per-image stage (``RandomMotion``) draws one set per augmented image, always for the modality and then each kept
+        source, whether or not a batch will ask for the augmented target, so that a plan does not depend on that flag"""
         seed = int(torch.randint(0, 2 ** 62, (1,), generator=self._gen))
         stages = []
         with torch.random.fork_rng(devices=[]):
             torch.default_generator.manual_seed(seed)
             for t in self.transform:
                 if torch.rand(1).item() < t.p:
-                    params = t.sample()
+                    if t.per_image:
+                        params = {name: t.sample() for name in self._augmented_names()}
+                    else:
+                        params = t.sample()
                     if type(t) is augment.RandomSpike:
                         params = params._replace(path=self.spike_path(subject, stages))
                     stages.append((t, params))
         return seed, tuple(stages)
+
+    def _augmented_names(self) -> List[str]:
+        """the images of a subject that a batch can ask for augmented: the modality, then each kept source"""
+        return [self.modality] + [src for src in self.keep if src != self.modality]
 
     def _fill(self) -> None:
         if not self._order:
@@ -290,19 +306,20 @@ class PatchQueue:
     def split_stages(load: SubjectLoad) -> Tuple[tuple, tuple]:
         """(staged, fused): the stages up to and including the last non-local one that has an effect, applied once
         into a staging tensor, and the local stages after it, fused into the gather.  A non-local stage without an
-        effect (a blur whose three radii are 0, a ghosting or spike of intensity 0) is the identity and is dropped."""
+        effect (a blur whose three radii are 0, a ghosting or spike of intensity 0, a motion whose rotations and
+        translations are all 0) is the identity and is dropped."""
         live = [(t, p) for t, p in load.stages if type(t) not in _NONLOCAL or t.has_effect(p)]
         last = max((i for i, (t, _) in enumerate(live) if type(t) in _NONLOCAL), default=-1)
         return tuple(live[:last + 1]), tuple(live[last + 1:])
 
     def _staged_source(self, load: SubjectLoad, staged: tuple, name: str) -> torch.Tensor:
         """chain(crop_or_pad(raw)) through ``staged`` for one image of one load, made once and kept while the load has
-        patches"""
+        patches; a per-image stage applies the parameter set of the image it stages"""
         entry = self._staged.setdefault(id(load), (load, {}))[1]
         if name not in entry:
             x = augment.crop_or_pad(self._by_index[load.subject][name][DATA], self.target_shape, self.padding_value)
             for t, params in staged:
-                x = t.apply(x, params)
+                x = t.apply(x, params[name] if t.per_image else params)
             entry[name] = x
         return entry[name]
 
