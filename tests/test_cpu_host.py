@@ -195,6 +195,43 @@ def test_weight_pack_index_algebra_matches_conv_definitions():
     np.testing.assert_allclose(out, refd, rtol=1e-10, atol=1e-10)
 
 
+def test_weight_pack_entry_points_validate_before_any_launch():
+    """mi355_weight_pack and mi355_weight_pack_multi share one descriptor validation; the single entry point adds its dtype and
+    q_amax checks, the list entry point checks the dtype of the list up front.  Every case returns before a launch (no GPU)."""
+    from unet_bssfp_amd import _lib
+    lib = _lib.load()
+
+    def desc(**kw):
+        d = _lib.WpackDesc(src=0x1000, dst=0x2000, cout=32, cin=16, coutp=32, cinp=16, ks=1, s_co=16, s_ci=1,
+                           dtype=_lib.DT_BF16, s2d_mode=0, s2d_cp=0, q_amax=None)
+        d.s_k[:] = (1, 1, 1)
+        d.tstep[:] = (1, 1, 1)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def single(d):
+        return lib.mi355_weight_pack(ctypes.byref(d) if d is not None else None, None)
+
+    def multi(d):
+        return lib.mi355_weight_pack_multi(ctypes.byref(d) if d is not None else None, 1, None)
+
+    cases = [  # (descriptor, message of mi355_weight_pack, message of mi355_weight_pack_multi)
+        (None, b"weight_pack: null pointer", b"weight_pack_multi: bad argument"),
+        (desc(src=None), b"weight_pack: null pointer", b"weight_pack: null pointer"),
+        (desc(coutp=48, cout=48), b"weight_pack: bad extents", b"weight_pack: bad extents"),
+        (desc(s2d_mode=3, s2d_cp=8), b"weight_pack: bad space-to-depth mode", b"weight_pack: bad space-to-depth mode"),
+        (desc(dtype=2), b"weight_pack: bad dtype", b"weight_pack_multi: bad dtype"),
+        (desc(dtype=_lib.DT_FP8), b"weight_pack: fp8 packing needs q_amax", None),      # the list entry point has no such check
+    ]
+    for d, msg_single, msg_multi in cases:
+        assert single(d) < 0
+        assert msg_single in lib.mi355_last_error()
+        if msg_multi is not None:
+            assert multi(d) < 0
+            assert msg_multi in lib.mi355_last_error()
+
+
 def test_lds_dma_kernels_contain_no_compiler_generated_m0_use():
     """common.h: dma_lds_b128 overwrites m0 inside an asm statement and cannot declare it (hipcc rejects the clobber).  That is safe
     only while the compiler itself neither sets nor reads m0 in those kernels: no movrel / s_set_gpr_idx (dynamically indexed

@@ -1,14 +1,17 @@
 #!/bin/bash
 # Timing-only variants of the C-ABI library (tools/_build/, never shipped): the other objects come from the diagnostic build
-# (tools/build_diag.sh), conv_api.o is recompiled per variant.  usage: tools/build_variants.sh name1="-DX -DY" name2="-DZ" ...
+# (tools/build_diag.sh), the convolution API object is recompiled per variant (csrc/Makefile: variant).
+# usage: tools/build_variants.sh name1="-DX -DY" name2="-DZ" ...
 set -e
 cd "$(dirname "$0")/.."
-[ -f tools/_build/runtime.o ] || bash tools/build_diag.sh
-OTHERS=""
-for f in runtime wgrad elementwise upcat dti patches metrics augment; do OTHERS="$OTHERS tools/_build/$f.o"; done
+MK=(make -s -C unet_bssfp_amd/csrc OBJDIR="$PWD/tools/_build" EXTRA_CXXFLAGS="-DMI355_DIAG $MI355_DIAG_FLAGS")
+mkdir -p tools/_build
+# Objects that are missing or older than a source are compiled once, here, with the diagnostic build's flags; no diagnostic
+# library is linked.  make does not track flags: an up-to-date object keeps those of the call that compiled it
+# (tools/build_diag.sh recompiles everything).
+"${MK[@]}" -j8 objs
 for spec in "$@"; do
   name=${spec%%=*}; flags=${spec#*=}
-  ( /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DMI355_DIAG $flags -c unet_bssfp_amd/csrc/conv_api.hip -o tools/_build/conv_api_$name.o &&
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/_build/libmi355_unet_$name.so tools/_build/conv_api_$name.o $OTHERS && echo built $name ) &
+  ( "${MK[@]}" variant NAME="$name" VARIANT_FLAGS="$flags" && echo built $name ) &
 done
 wait

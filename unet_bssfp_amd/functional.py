@@ -112,7 +112,7 @@ S2D_POISON = False      # tests: fill new space-to-depth tensors with NaN to pro
 
 def _new_s2d(shape, dtype, device):
     """A space-to-depth output tensor.  Not zero-filled: the pack / norm+act kernels write every (cell, block) slot, the
-    out-of-volume blocks of the border cells included (elementwise.hip: s2d_zero_siblings)."""
+    out-of-volume blocks of the border cells included (elementwise_common.h: s2d_zero_siblings)."""
     if S2D_POISON:
         return torch.full(shape, float("nan"), dtype=dtype, device=device)
     return torch.empty(shape, dtype=dtype, device=device)
