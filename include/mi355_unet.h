@@ -519,6 +519,25 @@ int mi355_ssim3d(const float* x, const float* y, int32_t items, int32_t c, int32
                  int64_t workspace_bytes, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SSIM as a reconstruction-loss term (the reference's objective sums L1, 1 - SSIM and the
+ * Perceptual term): mi355_ssim3d with a backward for its FIRST argument.  Same inputs, window
+ * and per-item f64 result as mi355_ssim3d.
+ *   workspace_bytes: one size serves both calls; -1 for a bad shape.
+ *   fwd: ssim[item] = mean SSIM; p = 3 f32 fields of items*c*(d-win+1)*(h-win+1)*(w-win+1) elements,
+ *        the local derivatives dS/d(G*x), dS/d(G*xx), dS/d(G*xy) at every window position.
+ *   bwd: dx = grad[item] * d ssim[item] / d x (f32, shape of x); `grad` = DEVICE vector of `items`
+ *        f32 values, read by the kernel (no host read: the call can be recorded into a hipGraph).
+ *        Gather form, no atomics: bit-identical between calls.
+ * ---------------------------------------------------------------------------------------- */
+int64_t mi355_ssim3d_loss_workspace_bytes(int32_t items, int32_t c, int32_t d, int32_t h, int32_t w, int32_t win);
+int mi355_ssim3d_loss_fwd(const float* x, const float* y, int32_t items, int32_t c, int32_t d, int32_t h, int32_t w,
+                          int32_t win, const float* window, float c1, float c2, void* workspace,
+                          int64_t workspace_bytes, double* ssim, float* p, void* stream);
+int mi355_ssim3d_loss_bwd(const float* x, const float* y, const float* p, const float* grad, int32_t items,
+                          int32_t c, int32_t d, int32_t h, int32_t w, int32_t win, const float* window,
+                          void* workspace, int64_t workspace_bytes, float* dx, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Intensity augmentations of the training transform (src/data_module.py:130-139), GPU side:
  * tio.RandomBiasField (x * exp(polynomial field), `coefficients` = HOST array of
  * (order+1)(order+2)(order+3)/6 values in TorchIO's x-y-z loop order, order <= 4), tio.RandomGamma

@@ -1532,6 +1532,25 @@ def l1_loss(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return L1LossFn.apply(a, b)
 
 
+class SSIM3dFn(Function):
+    """Per-item Gaussian-window SSIM of contiguous f32 (B, C, D, H, W) tensors, (B, 1) f32, differentiable in ``a`` only
+    (losses.SSIMLoss).  ``window``: the normalised 1-D profile, a host tensor.  The incoming per-item gradient stays on the
+    device (ops.ssim3d_loss_bwd), so a step with this term captures into a hipGraph."""
+
+    @staticmethod
+    def forward(ctx, a, b, window, c1: float, c2: float):
+        ssim, p = ops.ssim3d_loss_fwd(a, b, window, c1, c2)
+        ctx.save_for_backward(a, b, p)
+        ctx.window = window
+        return ssim.float()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, b, p = ctx.saved_tensors
+        return ops.ssim3d_loss_bwd(a, b, p, g, ctx.window), None, None, None, None
+
+
 class GanGenLossFn(Function):
     """The generator phase's loss head (src/model.py:126-137) as one launch each way on top of the L1 kernels:
     (adv + recon, [L1, recon, adv, adv + recon]) with adv = BCEWithLogits(logits, 1).mean() and recon = L1(y_hat, y) / divisor

@@ -1,0 +1,61 @@
+"""Loss terms on the GPU beyond L1 -- the reconstruction slot of ``gan.bSSFPToDWITensorModel``.
+
+The reference's objective sums L1, 1 - SSIM and the MedicalNet Perceptual term (thesis, 03-methods; src/model.py:209
+averages the terms of the slot).  ``SSIMLoss`` has the constructor signature of ``monai.losses.SSIMLoss``; MONAI is
+absent from this image, so parity with it is UNPINNED, as for ``metrics.SSIMMetric``: the formulas are the ones restated
+in oracle/metrics_ref.py, and the tests check value and gradient against that oracle in f64.  The Perceptual term needs
+remotely fetched weights and is not provided.
+
+    model = bSSFPToDWITensorModel("bssfp", extra_recon_terms={"SSIM": SSIMLoss(3)})   # recon = (L1 + SSIM) / 2 * recon_factor
+"""
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+from . import _lib
+from .functional import SSIM3dFn
+
+
+class SSIMLoss(nn.Module):
+    """``1 - SSIM(input, target)`` per batch item, reduced by ``mean`` / ``sum`` / ``none`` (``none``: (B, 1)).
+
+    Differentiable in ``input`` only (csrc/ssim_loss.hip); a ``target`` that requires grad is refused.  Any float dtype and
+    any strides: the tensors are made f32 and contiguous by ordinary torch ops, so autograd carries views and dtypes."""
+
+    def __init__(self, spatial_dims: int, data_range: float = 1.0, kernel_type: str = "gaussian", win_size: int = 11,
+                 kernel_sigma: float = 1.5, k1: float = 0.01, k2: float = 0.03, reduction: str = "mean"):
+        super().__init__()
+        if spatial_dims != 3:
+            raise NotImplementedError("only the reference's 3-D configuration is built")
+        if kernel_type != "gaussian":
+            raise NotImplementedError("only the Gaussian window (MONAI's default) is built")
+        if not 1 <= win_size <= 15:
+            raise ValueError("win_size must be in 1..15")
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f'Unsupported reduction: {reduction}, available options are ["mean", "sum", "none"].')
+        self.spatial_dims, self.data_range, self.kernel_type, self.win_size = spatial_dims, data_range, kernel_type, win_size
+        self.kernel_sigma, self.k1, self.k2, self.reduction = kernel_sigma, k1, k2, reduction
+        dist = torch.arange(start=(1 - win_size) / 2, end=(1 + win_size) / 2, step=1)
+        g = torch.exp(-torch.pow(dist / kernel_sigma, 2) / 2)
+        self._window = (g / g.sum()).float().contiguous()             # host side: travels by value
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if not (input.is_cuda and target.is_cuda):
+            raise _lib.Mi355Error("SSIMLoss runs on the GPU only (no CPU fallback)")
+        if input.shape != target.shape:
+            raise ValueError(f"input and target should have same shapes, got {tuple(input.shape)} and {tuple(target.shape)}.")
+        if input.dim() != 5:
+            raise ValueError(f"input should have 5 dimensions (batch, channel, D, H, W), got {input.dim()}.")
+        if min(input.shape[2:]) < self.win_size:
+            raise ValueError(f"spatial size {tuple(input.shape[2:])} is smaller than the {self.win_size}-wide window")
+        if target.requires_grad:
+            raise NotImplementedError("only the gradient with respect to `input` is built; detach `target`")
+        c1, c2 = (self.k1 * self.data_range) ** 2, (self.k2 * self.data_range) ** 2
+        ssim = SSIM3dFn.apply(input.float().contiguous(), target.detach().float().contiguous(), self._window, c1, c2)
+        loss = 1 - ssim
+        if self.reduction == "mean":
+            return loss.mean()
+        if self.reduction == "sum":
+            return loss.sum()
+        return loss

@@ -873,6 +873,43 @@ def l1_bwd(a, b, gscale: torch.Tensor) -> torch.Tensor:
     return da
 
 
+def _ssim_loss_args(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor):
+    require_cuda(x, y)
+    assert x.dtype == y.dtype == torch.float32 and x.is_contiguous() and y.is_contiguous() and x.shape == y.shape and x.dim() == 5
+    assert not window.is_cuda and window.dtype == torch.float32 and window.is_contiguous()      # travels by value
+    lib = _lib.load()
+    win = window.numel()
+    need = lib.mi355_ssim3d_loss_workspace_bytes(*x.shape, win)
+    if need < 0:
+        raise ValueError(f"spatial size {tuple(x.shape[2:])} is smaller than the {win}-wide window")
+    return lib, win, need, window.numpy().ctypes.data_as(C.c_void_p)
+
+
+def ssim3d_loss_fwd(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, c1: float, c2: float):
+    """-> (ssim (B, 1) f64 as metrics.SSIMMetric computes it, p = the three derivative fields the backward reads)"""
+    lib, win, need, wptr = _ssim_loss_args(x, y, window)
+    n, c, d, h, w = x.shape
+    work = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ssim = torch.empty((n, 1), dtype=torch.float64, device=x.device)
+    p = torch.empty((3, n, c, d - win + 1, h - win + 1, w - win + 1), dtype=torch.float32, device=x.device)
+    _lib.check(lib.mi355_ssim3d_loss_fwd(x.data_ptr(), y.data_ptr(), n, c, d, h, w, win, wptr, c1, c2, work.data_ptr(), need,
+                                         ssim.data_ptr(), p.data_ptr(), _stream()), "ssim3d_loss_fwd")
+    return ssim, p
+
+
+def ssim3d_loss_bwd(x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, grad: torch.Tensor, window: torch.Tensor) -> torch.Tensor:
+    """grad: one value per batch item, on the device -> grad[b] * d ssim[b] / d x"""
+    lib, win, need, wptr = _ssim_loss_args(x, y, window)
+    require_cuda(p, grad)
+    n, c, d, h, w = x.shape
+    g = grad.to(torch.float32).reshape(n).contiguous()
+    work = torch.empty(need, dtype=torch.uint8, device=x.device)
+    dx = torch.empty_like(x)
+    _lib.check(lib.mi355_ssim3d_loss_bwd(x.data_ptr(), y.data_ptr(), p.data_ptr(), g.data_ptr(), n, c, d, h, w, win, wptr,
+                                         work.data_ptr(), need, dx.data_ptr(), _stream()), "ssim3d_loss_bwd")
+    return dx
+
+
 def gan_gen_loss_fwd(logits: torch.Tensor, y_hat: torch.Tensor, y: torch.Tensor, divisor: float, factor: float) -> torch.Tensor:
     """-> f32[4] = (L1(y_hat, y), L1 / divisor * factor, mean BCEWithLogits(logits, 1), their sum): src/model.py:126-137"""
     require_cuda(logits, y_hat, y)
