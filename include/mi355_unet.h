@@ -650,6 +650,21 @@ int mi355_rigid_resample(const float* x, float* out, int32_t c, int32_t d, int32
 int mi355_aug_motion(const float* x, float* out, int32_t c, int32_t d, int32_t h, int32_t w, int32_t nimg, const float* m,
                      const float* band_matrices, const double* channel_min, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Epoch statistics of the fit loop (unet_bssfp_amd/trainer.py: EpochStats) -- the epoch means behind the reference's
+ * `self.log(..., on_epoch=True, sync_dist=True)` calls (src/model.py:178, 205, 210, 218, 266, 276, 286).
+ * table: HOST struct of n DEVICE pointers, each to one f32 scalar (the step's log values; the same address may appear in
+ * several slots); it travels by value in the kernel arguments, so the call can be recorded into a hipGraph.
+ * acc: DEVICE, 2n + 1 doubles, zeroed by the caller at the start of an epoch:
+ *     acc[k] += weight * (double)*src[k]   (k < n),   acc[n] += weight,   acc[n + 1 + k] += 1 if *src[k] is NaN or +-inf.
+ * A non-finite value enters its sum as IEEE arithmetic carries it and is counted as well.
+ * One launch of one 64-lane workgroup, lane k owns scalar k: plain loads and stores, no atomics, no LDS, no workspace.
+ * n < 1, n > MI355_EPOCH_MAX_SCALARS and null pointers are refused before any launch (acc is left as it was).
+ * ---------------------------------------------------------------------------------------- */
+#define MI355_EPOCH_MAX_SCALARS 32
+typedef struct mi355_scalar_table { const float* src[MI355_EPOCH_MAX_SCALARS]; } mi355_scalar_table;
+int mi355_epoch_accumulate(const mi355_scalar_table* table, int32_t n, double weight, double* acc, void* stream);
+
 /* layout probe used by the tests: writes lane -> (row, col) maps of the MFMA accumulators */
 int mi355_mfma_selftest(float* out_f32_1024, float* out_bf16_1024, void* stream);
 

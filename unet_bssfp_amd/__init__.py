@@ -8,6 +8,15 @@ from . import _lib  # noqa: F401
 from .nn import (BasicUNet, Conv3d, ConvTranspose3d, Discriminator, DownSampleConv, Generator,  # noqa: F401
                  compute_dtype_from_name, set_compute_dtype, set_default_compute_dtype)
 from .functional import l1_loss  # noqa: F401
+from .trainer import EarlyStopping, EpochStats, ModelCheckpoint, Trainer  # noqa: F401
 
 __all__ = ["BasicUNet", "Conv3d", "ConvTranspose3d", "Discriminator", "DownSampleConv", "Generator",
-           "compute_dtype_from_name", "set_compute_dtype", "set_default_compute_dtype", "l1_loss"]
+           "compute_dtype_from_name", "set_compute_dtype", "set_default_compute_dtype", "l1_loss",
+           "EarlyStopping", "EpochStats", "ModelCheckpoint", "Trainer", "train_model"]
+
+
+def __getattr__(name):
+    if name == "train_model":            # lazily: ``python -m unet_bssfp_amd.train`` must not find its module imported already
+        from .train import train_model
+        return train_model
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -77,6 +77,13 @@ class QueueSource(C.Structure):
     _fields_ = [("src", _vp), ("d", _i32), ("h", _i32), ("w", _i32)]
 
 
+EPOCH_MAX_SCALARS = 32          # MI355_EPOCH_MAX_SCALARS
+
+
+class ScalarTable(C.Structure):
+    _fields_ = [("src", _vp * EPOCH_MAX_SCALARS)]
+
+
 class NormSmallDesc(C.Structure):
     _fields_ = [("base", NormActDesc), ("eps", _f32), ("momentum", _f32), ("mean_out", _vp), ("rstd_out", _vp),
                 ("running_mean", _vp), ("running_var", _vp), ("batches_tracked", _vp), ("n_real", _i32),
@@ -163,6 +170,7 @@ _SIGNATURES = {
     "mi355_aug_spike_add": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _f32, _vp]),
     "mi355_rigid_resample": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp]),
     "mi355_aug_motion": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mi355_epoch_accumulate": (C.c_int, [C.POINTER(ScalarTable), _i32, C.c_double, _vp, _vp]),
     "mi355_mfma_selftest": (C.c_int, [_vp, _vp, _vp]),
     "mi355_amax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "mi355_amax_act": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _vp, _vp]),

@@ -65,7 +65,11 @@ def load_checkpoint(model, path: str, strict: bool = True, load_optimizers: bool
     """Load a checkpoint written by ``save_checkpoint`` or by the reference's Lightning run into ``model``.
     Returns {'epoch', 'global_step', 'ignored_keys'}; keys outside gen./discr. (the reference's
     ``recon_criterion.*`` etc.) are listed, not loaded."""
-    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    return apply_checkpoint(model, torch.load(path, map_location="cpu", weights_only=True), strict, load_optimizers, path)
+
+
+def apply_checkpoint(model, ckpt: Dict, strict: bool = True, load_optimizers: bool = True, path: str = "checkpoint") -> Dict:
+    """``load_checkpoint`` for a file that has been read already (the fit loop reads its own additions from the same dict)"""
     if "state_dict" not in ckpt:
         raise KeyError(f"{path}: not a Lightning-shaped checkpoint (no 'state_dict')")
     sd = ckpt["state_dict"]

@@ -184,6 +184,30 @@ class PatchQueue:
     def __len__(self):
         return len(self.subjects) * self.samples_per_volume
 
+    # ---- state at an epoch boundary --------------------------------------------------------------------------------
+    def _drained(self) -> bool:
+        self._release_staged(())             # staging tensors of loads whose last patch has been gathered are dead
+        return not self._patches and not self._order and not self._staged
+
+    def state_dict(self) -> Dict:
+        """``{'generator': uint8 tensor, 'epoch', 'fill_count'}`` -- all a queue carries from one epoch into the next.  Valid
+        only when the queue is drained (no pending patch, no subject left in the epoch, nothing staged), which is where a
+        whole number of epochs of ``batches()`` / ``next_plan(len(queue))`` leaves it; otherwise ``RuntimeError``: a queue in
+        the middle of an epoch is not resumable.  A fresh queue over the same subjects and arguments that loads the state
+        plans the following epochs identically: same subjects, load seeds, stages and origins."""
+        if not self._drained():
+            raise RuntimeError("PatchQueue.state_dict: the queue is in the middle of an epoch "
+                               f"({len(self._patches)} patches pending, {len(self._order)} subjects left, "
+                               f"{len(self._staged)} loads staged); its state is defined at epoch boundaries only")
+        return {"generator": self._gen.get_state().clone(), "epoch": int(self.epoch), "fill_count": int(self.fill_count)}
+
+    def load_state_dict(self, state: Dict) -> None:
+        if not self._drained():
+            raise RuntimeError("PatchQueue.load_state_dict: the queue is in the middle of an epoch")
+        self._gen.set_state(torch.as_tensor(state["generator"], dtype=torch.uint8).cpu())
+        self.epoch, self.fill_count = int(state["epoch"]), int(state["fill_count"])
+        self.last_fill = []
+
     def _check_nonlocal(self) -> None:
         """what a staged stage cannot do is refused here, not at the first load in which the stage happens to fire"""
         limit = augment.AXIS_MAX_N

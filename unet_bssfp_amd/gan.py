@@ -472,10 +472,15 @@ class GraphedTrainingStep:
 
     The batch tensors are static inputs: ``load(batch)`` copies new volumes into them.  Dropout masks
     change per replay (device-side step counter), AdamW bias correction advances on the device.
+
+    The constructor runs ``max(2, warmup)`` real eager steps on ``batch`` before it captures.  ``preserve_state=True`` (the fit
+    loop, trainer.py) puts back, in place, everything they change -- parameters, BatchNorm statistics, optimiser state and
+    step counters, the dropout counter -- so that the capture does not train; it raises ``NotImplementedError`` with e4m3
+    operands, whose delayed-scale history cannot be un-primed.
     """
 
     def __init__(self, model: bSSFPToDWITensorModel, batch, warmup: int = 3, group=None, force_segments: bool = False,
-                 force_collectives: bool = False, broadcast_buffers_every: int = 0):
+                 force_collectives: bool = False, broadcast_buffers_every: int = 0, preserve_state: bool = False):
         import torch.distributed as dist
         self.model = model
         self.batch = batch
@@ -496,6 +501,10 @@ class GraphedTrainingStep:
             from . import ddp
             ddp.flatten_buffers(model)                       # one flat tensor per dtype: the per-step broadcast is one collective each, no copies
         self.launch_log = []                                # (what, position) of the latest step: tests
+        # preserve_state (trainer.Trainer): the warm-up steps below are real training steps on ``batch``.  A benchmark does not
+        # mind; a fit loop would train its first batch several times and a resumed run would differ from an uninterrupted
+        # one.  With preserve_state everything they change is put back IN PLACE after the capture (the graph holds addresses).
+        snapshot = self._snapshot_state() if preserve_state else None
         for _ in range(max(2, warmup)):                     # eager: allocations, caches, optimiser state
             self._eager_step()
         torch.cuda.synchronize()
@@ -508,7 +517,54 @@ class GraphedTrainingStep:
         # Every instance keeps its OWN log tensors (its capture's outputs): ``__call__(i)`` points ``model.last_logs`` at them.
         self.instances = [(batch, self.graphs, self.logs)]
         model.last_logs = self.logs
+        if snapshot is not None:
+            self._restore_state(snapshot)
         torch.cuda.synchronize()
+
+    def _snapshot_state(self):
+        """Device clones of what the warm-up steps and the capture change: every tensor of ``model.state_dict()`` (parameters,
+        BatchNorm running statistics, ``num_batches_tracked``), both optimisers' state (moments, host ``step`` integers,
+        FusedAdamW's ``_calls`` and device step counters; empty on a fresh model) and the dropout step counter.  The delayed
+        e4m3 scale history (functional.Fp8Scales) cannot be un-primed, so e4m3 operands are refused."""
+        m = self.model
+        if any(getattr(mod, "fp8", False) for mod in m.modules()):
+            raise NotImplementedError("GraphedTrainingStep(preserve_state=True): the warm-up steps prime the delayed e4m3 scales "
+                                      "(functional.Fp8Scales), which cannot be put back; use bf16 or f32 operands")
+        from .functional import DropoutState
+        dev = next(m.gen.parameters()).device
+        opts = []
+        for o in m.optimizers():
+            state = {p: {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in st.items()}
+                     for p, st in o.state.items() if st}
+            opts.append((state, dict(getattr(o, "_calls", {})), {gi: t.clone() for gi, t in getattr(o, "_step_dev", {}).items()}))
+        return {"model": {k: v.detach().clone() for k, v in m.state_dict().items()}, "optimizers": opts,
+                "dropout": DropoutState.base(dev).clone()}
+
+    @torch.no_grad()
+    def _restore_state(self, snap):
+        """Put the snapshot back in place: ``copy_`` into the existing parameter, buffer and moment tensors, ``copy_`` / ``zero_``
+        the existing device counters, reset the host integers; state that the warm-up created (a fresh model had none) is
+        zeroed, which is the state AdamW starts from.  Then re-pack both networks' weights into their existing buffers, as the
+        captured step itself does after each optimiser step."""
+        m = self.model
+        from .functional import DropoutState, repack_weights
+        for k, v in m.state_dict().items():
+            v.copy_(snap["model"][k])
+        for o, (state, calls, counters) in zip(m.optimizers(), snap["optimizers"]):
+            for p, st in o.state.items():
+                old = state.get(p)
+                for k, v in list(st.items()):
+                    if isinstance(v, torch.Tensor):
+                        v.zero_() if old is None else v.copy_(old[k])
+                    else:
+                        st[k] = type(v)(0) if old is None else old[k]
+            if hasattr(o, "_step_dev"):
+                for gi, t in o._step_dev.items():
+                    t.copy_(counters[gi]) if gi in counters else t.zero_()
+                o._calls = dict(calls)
+        DropoutState.base(next(m.gen.parameters()).device).copy_(snap["dropout"])
+        repack_weights(m.gen)
+        repack_weights(m.discr)
 
     def _assert_fp8_slots_primed(self):
         """Delayed-scaling slots (functional.Fp8Scales) carry HOST flags that a capture bakes in: a slot that is touched but

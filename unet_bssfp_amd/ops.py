@@ -954,6 +954,29 @@ def gan_discr_loss_bwd(fake: torch.Tensor, real: torch.Tensor, upstream: torch.T
                                                     dfake.data_ptr(), dreal.data_ptr(), _stream()), "gan_discr_loss_bwd")
 
 
+def scalar_table(sources: Sequence[torch.Tensor]) -> _lib.ScalarTable:
+    """The by-value pointer table of ``epoch_accumulate``: one f32 device scalar per slot (the caller keeps them alive)"""
+    if len(sources) > _lib.EPOCH_MAX_SCALARS:
+        raise ValueError(f"at most {_lib.EPOCH_MAX_SCALARS} scalars per table, got {len(sources)}")
+    require_cuda(*sources)
+    table = _lib.ScalarTable()
+    for k, t in enumerate(sources):
+        if t.dtype != torch.float32 or t.numel() != 1:
+            raise ValueError(f"scalar {k}: need one float32 element, got {t.dtype} {tuple(t.shape)}")
+        table.src[k] = t.data_ptr()
+    return table
+
+
+def epoch_accumulate(table: _lib.ScalarTable, n: int, weight: float, acc: torch.Tensor):
+    """acc[k] += weight * *src[k] (k < n), acc[n] += weight, acc[n + 1 + k] += 1 for a non-finite *src[k]: one launch, no
+    host read.  ``acc``: 2n + 1 contiguous f64 on the device."""
+    require_cuda(acc)
+    if acc.dtype != torch.float64 or not acc.is_contiguous() or acc.numel() < 2 * max(n, 0) + 1:
+        raise ValueError(f"acc: need at least {2 * max(n, 0) + 1} contiguous float64 elements, got {acc.dtype} {tuple(acc.shape)}")
+    _lib.check(_lib.load().mi355_epoch_accumulate(C.byref(table), n, float(weight), acc.data_ptr(),
+                                                  torch.cuda.current_stream(acc.device).cuda_stream), "epoch_accumulate")
+
+
 def mfma_selftest(device) -> Tuple[torch.Tensor, torch.Tensor]:
     a = torch.zeros(1024, dtype=torch.float32, device=device)
     b = torch.zeros(1024, dtype=torch.float32, device=device)

@@ -121,7 +121,17 @@ class FusedAdamW(torch.optim.Optimizer):
             counter = self._step_dev.get(gi)
             if counter is None:
                 continue
-            t = int(counter.item())
+            self.set_step_counts(int(counter.item()), gi)
+
+    def set_step_counts(self, t: int, group_index=None):
+        """The host side of ``t`` steps taken: ``state['step']`` and the call count that ``step()`` compares it with.  A caller
+        that has counted its graph replays (trainer.Trainer) brings the host side up to date with this, without reading the
+        device counter, before it runs ``step()`` eagerly again: an eager step whose host integers lag behind the device
+        counter would take the host-side bias correction of the WRONG step."""
+        for gi, group in enumerate(self.param_groups):
+            if (group_index is not None and gi != group_index) or gi not in self._step_dev:
+                continue
+            self._calls[gi] = int(t)
             for p in group["params"]:
                 if self.state.get(p):
-                    self.state[p]["step"] = t
+                    self.state[p]["step"] = int(t)
