@@ -597,7 +597,7 @@ def test_discriminator_first_block_split_equals_the_unsplit_network(hip):
         d.load_state_dict(state)
         d = M.set_compute_dtype(d.to(DEV).train(), torch.bfloat16)
         d.split_first_block = split
-        Fn.DropoutState.advance(torch.device(DEV))                  # a new step: the per-step memos are empty
+        Fn.begin_step(torch.device(DEV))                  # a new step: the per-step memos are empty
         launches = []
         ops.CONV_PROBE = lambda pid, dd, real: launches.append((pid, bool(dd.addend)))
         try:

@@ -746,7 +746,7 @@ def test_batched_repack_matches_single_pack(hip, dtype):
         s, w = m.spec, m.weight
         cinp = ops.round_up(s.cin, 16)
         if s.kind == "conv" and s.stride == 1:
-            packed += [s.w_fwd(w, dtype, cinp)[0], s.w_dgrad_s1(w, dtype, ops.round_up(s.cout, 16), cinp)[0]]
+            packed += [s.w_fwd(w, dtype, cinp)[0], s.w_dgrad_s1(w, dtype, ops.round_up(s.cout, 16))[0]]
         elif s.kind == "conv":
             packed += [s.w_fwd_s2d(w, dtype, 32)[0], s.w_dgrad_s2d(w, dtype, 32, 32)[0]]
         else:
@@ -763,7 +763,7 @@ def test_batched_repack_matches_single_pack(hip, dtype):
         s, w = m.spec, m.weight
         cinp = ops.round_up(s.cin, 16)
         if s.kind == "conv" and s.stride == 1:
-            fresh = [s.w_fwd(w, dtype, cinp)[0], s.w_dgrad_s1(w, dtype, ops.round_up(s.cout, 16), cinp)[0]]
+            fresh = [s.w_fwd(w, dtype, cinp)[0], s.w_dgrad_s1(w, dtype, ops.round_up(s.cout, 16))[0]]
         elif s.kind == "conv":
             fresh = [s.w_fwd_s2d(w, dtype, 32)[0], s.w_dgrad_s2d(w, dtype, 32, 32)[0]]
         else:

@@ -296,7 +296,6 @@ class Fp8Scales:
                 ops.fp8_scale_roll(table, len(slots), sat)
                 for s in slots:
                     s.primed, s.touched = s.primed or s.touched, False
-        Fp8Side.clear()
 
     @classmethod
     def primed_slots(cls, device) -> set:
@@ -325,161 +324,93 @@ class Fp8Scales:
         return total
 
 
-class Fp8Side:
+class HandOver:
+    """A table that hands tensors from the launch that wrote them to the autograd node that consumes them, keyed by the
+    ADDRESS of the tensor they travel under (autograd hands tensors, not attributes, from one node to the next).  An entry
+    keeps that tensor alive, so the address cannot come to mean another tensor while the entry exists.  Every table
+    registers itself in ``per_step``: ``begin_step`` empties whatever is listed there."""
+    per_step = []               # everything with a clear() that a new training step empties (the memos below join it)
+
+    def __init__(self, doc: str, capacity: int = 8):
+        self.__doc__, self.capacity = doc, capacity
+        self.enabled = True     # read by the call sites only (bench.py's A/B switches)
+        self._by_ptr = {}
+        HandOver.per_step.append(self)
+
+    def put(self, t: torch.Tensor, *payload):
+        if len(self._by_ptr) >= self.capacity:     # (a loop that never starts a training step: nothing may pile up here)
+            self._by_ptr.clear()
+        self._by_ptr[t.data_ptr()] = (*payload, tuple(t.shape), t)
+
+    def take(self, t: torch.Tensor, keep: bool = False) -> Optional[tuple]:
+        """the payload registered under ``t`` (removed unless ``keep``), or None"""
+        hit = self._by_ptr.get(t.data_ptr()) if keep else self._by_ptr.pop(t.data_ptr(), None)
+        return hit[:-2] if hit is not None and hit[-2] == tuple(t.shape) else None
+
+    def clear(self):
+        self._by_ptr.clear()
+
+
+class _CheckedHandOver(HandOver):
+    """payload (y, weight, weight version): only the convolution it was computed for may take it"""
+
+    def take(self, a: torch.Tensor, w: torch.Tensor):
+        registered = a.data_ptr() in self._by_ptr
+        hit = super().take(a)
+        if registered and (hit is None or hit[1].data_ptr() != w.data_ptr() or hit[2] != w._version):
+            # (the activation may not even have been written: never fall back to a launch that would read it)
+            raise RuntimeError("FusedFinal: the convolution that takes the precomputed output is not the one it was computed for")
+        return hit[0] if registered else None
+
+
+Fp8Side = HandOver(
     """e4m3 copies on their way from the kernel that wrote them to the convolution that consumes them, keyed by the bf16
     tensor they mirror (autograd hands tensors, not attributes, from one node to the next).  An entry keeps its bf16 tensor
-    alive, so the address cannot come to mean another tensor while the entry exists.  Emptied every step."""
-    _by_ptr = {}
+    alive, so the address cannot come to mean another tensor while the entry exists.  Emptied every step.""", capacity=32)
 
-    @classmethod
-    def put(cls, t: torch.Tensor, t8: torch.Tensor):
-        if len(cls._by_ptr) >= 32:          # (a loop that never starts a training step: nothing may pile up here)
-            cls._by_ptr.clear()
-        cls._by_ptr[t.data_ptr()] = (t8, tuple(t.shape), t)
-
-    @classmethod
-    def take(cls, t: torch.Tensor, keep: bool = False) -> Optional[torch.Tensor]:
-        hit = cls._by_ptr.get(t.data_ptr()) if keep else cls._by_ptr.pop(t.data_ptr(), None)
-        return hit[0] if hit is not None and hit[1] == tuple(t.shape) else None
-
-    @classmethod
-    def clear(cls):
-        cls._by_ptr.clear()
-
-
-class ColSumSide:
+ColSumSide = HandOver(
     """Per-channel sums of a data gradient, emitted by the convolution launch that PRODUCED it (fused statistics epilogue),
     on their way to the node that needs them as a bias gradient (the transposed convolution under a skip concatenation:
-    its bias gradient was a separate pass over the full-resolution gradient).  Keyed like Fp8Side; emptied every step."""
-    _by_ptr = {}
-    enabled = True
+    its bias gradient was a separate pass over the full-resolution gradient).  Keyed like Fp8Side; emptied every step.
+    Payload: (partial sums, channel offset).""", capacity=32)
 
-    @classmethod
-    def put(cls, t: torch.Tensor, part: torch.Tensor, offset: int):
-        if len(cls._by_ptr) >= 32:
-            cls._by_ptr.clear()
-        cls._by_ptr[t.data_ptr()] = (part, offset, tuple(t.shape), t)
-
-    @classmethod
-    def take(cls, t: torch.Tensor):
-        hit = cls._by_ptr.pop(t.data_ptr(), None)
-        return (hit[0], hit[1]) if hit is not None and hit[2] == tuple(t.shape) else None
-
-    @classmethod
-    def clear(cls):
-        cls._by_ptr.clear()
-
-
-class LazyDx:
+LazyDx = HandOver(
     """A data gradient that is never materialised: the 1x1x1 final convolution of the U-Net hands (dz, W) to the norm + act
     node that produced its input, whose backward kernels form da = dz @ W per row on the fly (ops.normact_bwd, implicit=)
     instead of reading a 134-MB tensor twice that a separate launch would have written.  The convolution's backward returns an
     UNINITIALISED placeholder of da's shape (allocation only) and registers the operands under it; only a node that was
-    promised as the single consumer at forward time (ConvFn lazy_dx=True, set by BasicUNet) may receive it."""
-    _by_ptr = {}
-    enabled = True
+    promised as the single consumer at forward time (ConvFn lazy_dx=True, set by BasicUNet) may receive it.""")
 
-    @classmethod
-    def put(cls, placeholder: torch.Tensor, gz: torch.Tensor, gw: torch.Tensor):
-        if len(cls._by_ptr) >= 8:
-            cls._by_ptr.clear()
-        cls._by_ptr[placeholder.data_ptr()] = (gz, gw, tuple(placeholder.shape), placeholder)
-
-    @classmethod
-    def take(cls, t: torch.Tensor):
-        hit = cls._by_ptr.pop(t.data_ptr(), None)
-        return (hit[0], hit[1]) if hit is not None and hit[2] == tuple(t.shape) else None
-
-    @classmethod
-    def clear(cls):
-        cls._by_ptr.clear()
-
-
-class LazyPool:
+LazyPool = HandOver(
     """The gradient of an encoder level's output -- MaxPool3d(2)'s backward plus the skip connection's gradient -- never
-    materialised (round 4): ``SkipPoolFn.backward`` returns an UNINITIALISED placeholder and registers (idx, d_pool, d_skip) under
-    it; the norm + act node that produced the level's output forms da per row inside its two backward kernels
+    materialised (round 4): ``SkipPoolFn.backward`` returns an UNINITIALISED placeholder and registers (x, y, idx, d_pool,
+    d_skip) under it; the norm + act node that produced the level's output forms da per row inside its two backward kernels
     (``ops.normact_bwd(pool=)``: the window positions recorded by the forward max-pool, one byte per pooled element).  That drops
     the max-pool backward launch (at 128^3 x 32: 134 MB + 134 MB read, 134 MB written) and the two reads of its result; the
     values are those the launch would have stored, bit for bit.  Only offered when the producer of the pooled tensor IS a
     NormActFn node (checked on the autograd graph at forward time) and the extents are even; a node that cannot use it (the
-    small-tensor kernels, a space-to-depth output) materialises the gradient with the ordinary kernel."""
-    _by_ptr = {}
-    enabled = True              # bench.py --eager-pool-bwd turns it off (A/B)
+    small-tensor kernels, a space-to-depth output) materialises the gradient with the ordinary kernel.
+    ``enabled``: bench.py --eager-pool-bwd turns it off (A/B).""")
 
-    @classmethod
-    def put(cls, placeholder, x, y, idx, d_pool, d_skip):
-        if len(cls._by_ptr) >= 8:
-            cls._by_ptr.clear()
-        cls._by_ptr[placeholder.data_ptr()] = (x, y, idx, d_pool, d_skip, tuple(placeholder.shape), placeholder)
-
-    @classmethod
-    def take(cls, t):
-        hit = cls._by_ptr.pop(t.data_ptr(), None)
-        return hit[:5] if hit is not None and hit[5] == tuple(t.shape) else None
-
-    @classmethod
-    def clear(cls):
-        cls._by_ptr.clear()
-
-
-class PoolSide:
+PoolSide = HandOver(
     """MaxPool3d(2) of an activation that the norm + act launch producing it has already computed (ops.normact_fwd, pool=True):
-    NormActFn.forward registers (y, idx) under the activation, SkipPoolFn.forward takes them instead of launching."""
-    _by_ptr = {}
-    enabled = True              # bench.py --separate-pool turns it off (A/B)
+    NormActFn.forward registers (y, idx) under the activation, SkipPoolFn.forward takes them instead of launching.
+    ``enabled``: bench.py --separate-pool turns it off (A/B).""")
 
-    @classmethod
-    def put(cls, a, y, idx):
-        if len(cls._by_ptr) >= 8:
-            cls._by_ptr.clear()
-        cls._by_ptr[a.data_ptr()] = (y, idx, tuple(a.shape), a)
-
-    @classmethod
-    def take(cls, a):
-        hit = cls._by_ptr.pop(a.data_ptr(), None)
-        return (hit[0], hit[1]) if hit is not None and hit[2] == tuple(a.shape) else None
-
-    @classmethod
-    def clear(cls):
-        cls._by_ptr.clear()
-
-
-class FusedFinal:
+FusedFinal = _CheckedHandOver(
     """Output of a 1x1x1 convolution that the norm + act launch producing its input has already computed (ops.normact_fwd,
     final=): NormActFn.forward registers it under the activation, ConvFn.forward (lazy_dx=True: same single-consumer promise as
     LazyDx) takes it instead of launching.  The convolution stays an autograd node: its weight / bias gradients and the LazyDx
-    hand-over are unchanged."""
-    _by_ptr = {}
-
-    @classmethod
-    def put(cls, a: torch.Tensor, y: torch.Tensor, w: torch.Tensor):
-        if len(cls._by_ptr) >= 8:
-            cls._by_ptr.clear()
-        cls._by_ptr[a.data_ptr()] = (y, w, w._version, tuple(a.shape), a)
-
-    @classmethod
-    def take(cls, a: torch.Tensor, w: torch.Tensor):
-        hit = cls._by_ptr.pop(a.data_ptr(), None)
-        if hit is None:
-            return None
-        if hit[3] != tuple(a.shape) or hit[1].data_ptr() != w.data_ptr() or hit[2] != w._version:
-            # (the activation may not even have been written: never fall back to a launch that would read it)
-            raise RuntimeError("FusedFinal: the convolution that takes the precomputed output is not the one it was computed for")
-        return hit[0]
-
-    @classmethod
-    def clear(cls):
-        cls._by_ptr.clear()
+    hand-over are unchanged.""")
 
 
 def fp8_operand(x: torch.Tensor, slot: "Fp8Scales.Slot", constant: bool = False) -> torch.Tensor:
     """The e4m3 copy of a convolution operand with the amax in ``slot.use``: the one its producer wrote if there is one;
     otherwise one cast pass with the previous step's amax (gathering this step's); on the slot's first step the in-step
     amax pass + cast.  constant: an input that enters several convolution calls of one step (the packed batch) is cast once."""
-    x8 = Fp8Side.take(x, keep=constant)
-    if x8 is not None:
-        return x8
+    hit = Fp8Side.take(x, keep=constant)
+    if hit is not None:
+        return hit[0]
     if slot.primed:
         x8 = ops.cast_fp8(x, slot.use, slot.next)
     else:
@@ -493,7 +424,7 @@ def fp8_operand(x: torch.Tensor, slot: "Fp8Scales.Slot", constant: bool = False)
 
 
 class PackMemo:
-    """Packed form of constant NCDHW inputs, valid within ONE training step (``clear()`` runs at the start of every
+    """Packed form of constant NCDHW inputs, valid within ONE training step (``begin_step`` clears it at the start of every
     step, so a benchmark that feeds the same batch again still packs it each step).  An entry is tied to the tensor
     OBJECT (weak reference) and its version counter, never to an address."""
     _store = {}
@@ -519,6 +450,9 @@ class PackMemo:
     @classmethod
     def clear(cls):
         cls._store.clear()
+
+
+HandOver.per_step.append(PackMemo)
 
 
 class PackFn(Function):
@@ -565,24 +499,17 @@ class PackFn(Function):
     @once_differentiable
     def backward(ctx, g):
         g = ops.as_act(g)
-        grads = []
+        need = ctx.needs_input_grad[2:]
         if ctx.s2d:
-            cp = g.shape[4] // 8
-            if ctx.split is not None:
-                full = ops.unpack_ncdhw_s2d(g, sum(ctx.split), ctx.dims, cp, 0)
-                pieces = torch.split(full, ctx.split, dim=1)
-                return (None, None, *[pc.contiguous() if ctx.needs_input_grad[2 + i] else None for i, pc in enumerate(pieces)])
-            for i, (off, c) in enumerate(ctx.offs):
-                grads.append(ops.unpack_ncdhw_s2d(g, c, ctx.dims, cp, off) if ctx.needs_input_grad[2 + i] else None)
-            return (None, None, *grads)
+            def unpack(c, off, cp=g.shape[4] // 8):
+                return ops.unpack_ncdhw_s2d(g, c, ctx.dims, cp, off)
+        else:
+            def unpack(c, off):
+                return ops.unpack_ncdhw(g, c, off)
         if ctx.split is not None:
-            full = ops.unpack_ncdhw(g, sum(ctx.split), 0)
-            pieces = torch.split(full, ctx.split, dim=1)
-            grads = [pc.contiguous() if ctx.needs_input_grad[2 + i] else None for i, pc in enumerate(pieces)]
-            return (None, None, *grads)
-        for i, (off, c) in enumerate(ctx.offs):
-            grads.append(ops.unpack_ncdhw(g, c, off) if ctx.needs_input_grad[2 + i] else None)
-        return (None, None, *grads)
+            pieces = torch.split(unpack(sum(ctx.split), 0), ctx.split, dim=1)
+            return (None, None, *[pc.contiguous() if need[i] else None for i, pc in enumerate(pieces)])
+        return (None, None, *[unpack(c, off) if need[i] else None for i, (off, c) in enumerate(ctx.offs)])
 
 
 class UnpackFn(Function):
@@ -635,118 +562,142 @@ class ConvSpec:
         assert kind in ("conv", "deconv2")
         self.kind, self.cin, self.cout, self.ks, self.stride, self.pad = kind, cin, cout, ks, stride, pad
         self.cache = LayerCache()
-
-    # ---- packed weights --------------------------------------------------------------
-    def w_fwd(self, w, dtype, cinp):
-        k = self.ks
-        return self.cache.get(("fwd", dtype, cinp), w, lambda r: ops.weight_pack(
-            w.detach(), self.cout, self.cin, k, self.cin * k ** 3, k ** 3, (k * k, k, 1), (0, 0, 0), (1, 1, 1),
-            dtype, cinp, reuse=r))
-
-    def w_dgrad_s1(self, w, dtype, cinp, coutp_min):
-        k = self.ks
-        return self.cache.get(("dgrad", dtype, cinp), w, lambda r: ops.weight_pack(
-            w.detach(), self.cin, self.cout, k, k ** 3, self.cin * k ** 3, (k * k, k, 1), (k - 1,) * 3, (-1,) * 3,
-            dtype, cinp, reuse=r))
+        self._amax = {}             # cache key of an e4m3 packing -> its per-tensor max |w| (device f32[1], rewritten in place)
+        self._fp8_slots = {}        # (role, device) -> Fp8Scales.Slot
 
     def fp8_slot(self, role: str, device) -> "Fp8Scales.Slot":
         """delayed-scaling state of this layer's e4m3 operand: role 'x' (forward input) or 'g' (incoming gradient)"""
-        slots = self.__dict__.setdefault("_fp8_slots", {})
         key = (role, device)
-        if key not in slots:
-            slots[key] = Fp8Scales.slot(device)
-        return slots[key]
+        if key not in self._fp8_slots:
+            self._fp8_slots[key] = Fp8Scales.slot(device)
+        return self._fp8_slots[key]
 
-    # e4m3 packings (per-tensor scale 224 / max |w|): value = (packed, coutp, cinp, amax)
-    def _fp8(self, key, w, builder):
+    # ---- packed weights --------------------------------------------------------------
+    def _pack(self, key, w, geo, dtype, cinp, c_off=0, **opts):
+        """One packing of ``w`` through the cache.  geo: ops.weight_pack's (cout, cin, ks, s_co, s_ci, s_k, tbase, tstep); c_off:
+        first input channel of a channel slice (k^3 source elements each); opts: coutp, s2d_mode, s2d_cp.  dtype ops.FP8 (per-tensor
+        scale 224 / max |w|): the amax pass runs first and the value is (packed, coutp, cinp, amax)."""
         def build(reuse):
-            amax = ops.amax_f32(w.detach(), out=self._amax.get(key))
-            self._amax[key] = amax
-            packed, coutp, cinp = builder(reuse, amax)
-            return packed, coutp, cinp, amax
-        if not hasattr(self, "_amax"):
-            self._amax = {}
+            kw = dict(opts, reuse=reuse, src_offset=c_off * self.ks ** 3)
+            if dtype != ops.FP8:
+                return ops.weight_pack(w.detach(), *geo, dtype, cinp, **kw)
+            amax = self._amax[key] = ops.amax_f32(w.detach(), out=self._amax.get(key))
+            return (*ops.weight_pack(w.detach(), *geo, dtype, cinp, q_amax=amax, **kw), amax)
         return self.cache.get(key, w, build)
 
+    def w_fwd(self, w, dtype, cinp):
+        return self.w_fwd_part(w, dtype, cinp, 0, self.cin)
+
+    def w_dgrad_s1(self, w, dtype, cinp):
+        return self.w_dgrad_s1_part(w, dtype, cinp, 0, self.cin)
+
     def w_fwd8(self, w, cinp):
-        k = self.ks
-        return self._fp8(("fwd8", cinp), w, lambda r, amax: ops.weight_pack(
-            w.detach(), self.cout, self.cin, k, self.cin * k ** 3, k ** 3, (k * k, k, 1), (0, 0, 0), (1, 1, 1),
-            ops.FP8, cinp, reuse=r, q_amax=amax))
+        return self.w_fwd(w, ops.FP8, cinp)
 
     def w_dgrad8(self, w, cinp):
+        return self.w_dgrad_s1(w, ops.FP8, cinp)
+
+    # channel slice [c_off, c_off + c_n) of a stride-1 weight: forward and data-gradient packings (UpCatConvFn's skip part)
+    def w_fwd_part(self, w, dtype, cinp, c_off, c_n):
         k = self.ks
-        return self._fp8(("dgrad8", cinp), w, lambda r, amax: ops.weight_pack(
-            w.detach(), self.cin, self.cout, k, k ** 3, self.cin * k ** 3, (k * k, k, 1), (k - 1,) * 3, (-1,) * 3,
-            ops.FP8, cinp, reuse=r, q_amax=amax))
+        return self._pack(("fwd", dtype, cinp, c_off, c_n), w,
+                          (self.cout, c_n, k, self.cin * k ** 3, k ** 3, (k * k, k, 1), (0, 0, 0), (1, 1, 1)), dtype, cinp, c_off)
+
+    def w_dgrad_s1_part(self, w, dtype, cinp, c_off, c_n):
+        k = self.ks
+        return self._pack(("dgrad", dtype, cinp, c_off, c_n), w,
+                          (c_n, self.cout, k, k ** 3, self.cin * k ** 3, (k * k, k, 1), (k - 1,) * 3, (-1,) * 3), dtype, cinp, c_off)
 
     def w_dgrad_s2(self, w, dtype, cinp, cls):
         # k4 s2 p1 transposed: parity class p per dim uses taps {3,1} (p=0) or {2,0} (p=1)
         k = self.ks
         tb = tuple(3 if p == 0 else 2 for p in cls)
-        return self.cache.get(("dgrad2", dtype, cinp, cls), w, lambda r: ops.weight_pack(
-            w.detach(), self.cin, self.cout, 2, k ** 3, self.cin * k ** 3, (k * k, k, 1), tb, (-2,) * 3, dtype, cinp, reuse=r))
+        return self._pack(("dgrad2", dtype, cinp, cls), w,
+                          (self.cin, self.cout, 2, k ** 3, self.cin * k ** 3, (k * k, k, 1), tb, (-2,) * 3), dtype, cinp)
 
     def w_deconv_fwd(self, w, dtype, cinp, cls):
         # ConvTranspose3d weight (Cin, Cout, 2,2,2): class = output parity = tap
-        return self.cache.get(("dfwd", dtype, cinp, cls), w, lambda r: ops.weight_pack(
-            w.detach(), self.cout, self.cin, 1, 8, self.cout * 8, (4, 2, 1), cls, (0, 0, 0), dtype, cinp, reuse=r))
+        return self._pack(("dfwd", dtype, cinp, cls), w, (self.cout, self.cin, 1, 8, self.cout * 8, (4, 2, 1), cls, (0, 0, 0)),
+                          dtype, cinp)
 
     def w_deconv_fwd_all(self, w, dtype, cinp):
         # all 8 parity classes as ONE GEMM: column blk*Cout + co  <-  w[ci][co][(bd,bh,bw)]
-        return self.cache.get(("dfwd_all", dtype, cinp), w, lambda r: ops.weight_pack(
-            w.detach(), self.cout, self.cin, 1, 8, self.cout * 8, (4, 2, 1), (0, 0, 0), (0, 0, 0), dtype, cinp,
-            coutp=8 * self.cout, s2d_mode=2, s2d_cp=self.cout, reuse=r))
+        return self._pack(("dfwd_all", dtype, cinp), w, (self.cout, self.cin, 1, 8, self.cout * 8, (4, 2, 1), (0, 0, 0), (0, 0, 0)),
+                          dtype, cinp, coutp=8 * self.cout, s2d_mode=2, s2d_cp=self.cout)
 
     def w_deconv_dgrad(self, w, dtype, cinp):
-        return self.cache.get(("ddgrad", dtype, cinp), w, lambda r: ops.weight_pack(
-            w.detach(), self.cin, self.cout, 2, self.cout * 8, 8, (4, 2, 1), (0, 0, 0), (1, 1, 1), dtype, cinp, reuse=r))
+        return self._pack(("ddgrad", dtype, cinp), w, (self.cin, self.cout, 2, self.cout * 8, 8, (4, 2, 1), (0, 0, 0), (1, 1, 1)),
+                          dtype, cinp)
 
     # k4 s2 p1 on a space-to-depth input (dense k2 s1): W'[j][co][blk*cp + c] = w[co][c][2j + b]
     def w_fwd_s2d(self, w, dtype, cp):
-        k = self.ks
-        return self.cache.get(("fwd_s2d", dtype, cp), w, lambda r: ops.weight_pack(
-            w.detach(), self.cout, self.cin, 2, self.cin * k ** 3, k ** 3, (k * k, k, 1), (0, 0, 0), (2, 2, 2),
-            dtype, cinp=8 * cp, s2d_mode=1, s2d_cp=cp, reuse=r))
+        return self.w_fwd_s2d_part(w, dtype, cp, 0, self.cin)
 
     def w_dgrad_s2d(self, w, dtype, cinp, cp):
         # dS[i][blk*cp + c] = sum_{j'} dz[i + j' - 1][co] * w[co][c][2(1-j') + b]
-        k = self.ks
-        return self.cache.get(("dgrad_s2d", dtype, cinp, cp), w, lambda r: ops.weight_pack(
-            w.detach(), self.cin, self.cout, 2, k ** 3, self.cin * k ** 3, (k * k, k, 1), (2, 2, 2), (-2, -2, -2),
-            dtype, cinp=cinp, coutp=8 * cp, s2d_mode=2, s2d_cp=cp, reuse=r))
-
-    # channel slice [c_off, c_off + c_n) of a stride-1 weight: forward and data-gradient packings (UpCatConvFn's skip part)
-    def w_fwd_part(self, w, dtype, cinp, c_off, c_n):
-        k = self.ks
-        return self.cache.get(("fwd_part", dtype, cinp, c_off, c_n), w, lambda r: ops.weight_pack(
-            w.detach(), self.cout, c_n, k, self.cin * k ** 3, k ** 3, (k * k, k, 1), (0, 0, 0), (1, 1, 1),
-            dtype, cinp, reuse=r, src_offset=c_off * k ** 3))
-
-    def w_dgrad_s1_part(self, w, dtype, cinp, c_off, c_n):
-        k = self.ks
-        return self.cache.get(("dgrad_part", dtype, cinp, c_off, c_n), w, lambda r: ops.weight_pack(
-            w.detach(), c_n, self.cout, k, k ** 3, self.cin * k ** 3, (k * k, k, 1), (k - 1,) * 3, (-1,) * 3,
-            dtype, cinp, reuse=r, src_offset=c_off * k ** 3))
+        return self.w_dgrad_s2d_part(w, dtype, cinp, cp, 0, self.cin)
 
     # channel slice [c_off, c_off + c_n) of the k4 s2 p1 weight in the space-to-depth packings (the PatchGAN's first block
     # split into the parts of cat([x, y], 1): SplitS2dConvFn)
     def w_fwd_s2d_part(self, w, dtype, cp, c_off, c_n):
         k = self.ks
-        return self.cache.get(("fwd_s2d_part", dtype, cp, c_off, c_n), w, lambda r: ops.weight_pack(
-            w.detach(), self.cout, c_n, 2, self.cin * k ** 3, k ** 3, (k * k, k, 1), (0, 0, 0), (2, 2, 2),
-            dtype, cinp=8 * cp, s2d_mode=1, s2d_cp=cp, reuse=r, src_offset=c_off * k ** 3))
+        return self._pack(("fwd_s2d", dtype, cp, c_off, c_n), w,
+                          (self.cout, c_n, 2, self.cin * k ** 3, k ** 3, (k * k, k, 1), (0, 0, 0), (2, 2, 2)), dtype, 8 * cp, c_off,
+                          s2d_mode=1, s2d_cp=cp)
 
     def w_dgrad_s2d_part(self, w, dtype, cinp, cp, c_off, c_n):
         k = self.ks
-        return self.cache.get(("dgrad_s2d_part", dtype, cinp, cp, c_off, c_n), w, lambda r: ops.weight_pack(
-            w.detach(), c_n, self.cout, 2, k ** 3, self.cin * k ** 3, (k * k, k, 1), (2, 2, 2), (-2, -2, -2),
-            dtype, cinp=cinp, coutp=8 * cp, s2d_mode=2, s2d_cp=cp, reuse=r, src_offset=c_off * k ** 3))
+        return self._pack(("dgrad_s2d", dtype, cinp, cp, c_off, c_n), w,
+                          (c_n, self.cout, 2, k ** 3, self.cin * k ** 3, (k * k, k, 1), (2, 2, 2), (-2, -2, -2)), dtype, cinp, c_off,
+                          coutp=8 * cp, s2d_mode=2, s2d_cp=cp)
 
     def out_extent(self, e):
         if self.kind == "deconv2":
             return 2 * e
         return (e + 2 * self.pad - self.ks) // self.stride + 1
+
+
+def _conv_fwd_stats(want, x0, x1, wp, coutp, bias, ks, stride, pad, out, grid, real, cols=None, delta=None, **kw):
+    """ops.conv_fwd with, if wanted, the fused per-tile channel statistics: the buffer ([tiles][2][cols], cols = coutp unless
+    given) is sized by ops.conv_num_tiles for exactly this launch (kw: what both take -- fp8, addend, d2s).  Returns it, or None."""
+    part = None
+    if want:
+        tiles, _ = ops.conv_num_tiles(x0, x1, wp, coutp, ks, stride, pad, out, grid, **kw)
+        part = torch.empty((tiles, 2, cols or coutp), dtype=torch.float32, device=out.device)
+    ops.conv_fwd(x0, x1, wp, coutp, bias, ks, stride, pad, out, grid, stats=part, real=real, delta=delta, **kw)
+    return part
+
+
+def _out_and_stats(ctx, out, part):
+    """what the convolution nodes return: (out, statistics); without statistics an empty tensor stands in for them"""
+    if part is None:
+        part = torch.empty((0,), dtype=torch.float32, device=out.device)
+    ctx.mark_non_differentiable(part)
+    ctx.set_materialize_grads(False)      # no zero tensor (+ fill launch) for the statistics output in every backward
+    return out, part
+
+
+def _grad_target(p, deferrable=False):
+    """Where a parameter gradient goes: (sink, tensor the kernels write, accumulate?, deferred jobs).  With gradient storage owned
+    by the path (gradsink.GradBuckets) the kernels write -- or, for a second use of the parameter in this backward pass,
+    accumulate -- straight into ``p.grad`` and autograd gets None; otherwise a fresh tensor goes back to autograd.  deferrable:
+    the slab reductions of this contribution may be left to DeferredReduce (jobs is then a list for ops.conv_wgrad(defer=))."""
+    sink = sink_of(p)
+    if sink is None:
+        return None, torch.empty_like(p, dtype=torch.float32), False, None
+    jobs = [] if (deferrable and DeferredReduce.wants(sink, p, not sink.fresh(p))) else None
+    return sink, sink_grad(p), not sink.fresh(p), jobs      # (fresh: read AFTER wants(), which may have flushed p's first contribution)
+
+
+def _grad_done(sink, p, grad, jobs=None):
+    """The launches that write ``grad`` (see _grad_target) are enqueued: owe or tell the sink; returns what autograd gets."""
+    if jobs:
+        DeferredReduce.add(jobs, sink, p)
+    elif sink is not None:
+        sink.written(p)
+    else:
+        return grad
+    return None
 
 
 class ConvFn(Function):
@@ -775,14 +726,10 @@ class ConvFn(Function):
             do_, ho, wo = (spec.out_extent(e) for e in (di, hi, wi))
         out = ops.new_act(n, do_, ho, wo, cp, dtype, dev)
         part = None
+        bp = bias.detach() if bias is not None else None
         if s2d_cp:
             wp, coutp, _ = spec.w_fwd_s2d(weight, dtype, s2d_cp)
-            bp = bias.detach() if bias is not None else None
-            if want_stats:
-                tiles, _ = ops.conv_num_tiles(x0, None, wp, coutp, 2, 1, (0, 0, 0), out, (do_, ho, wo))
-                part = torch.empty((tiles, 2, coutp), dtype=torch.float32, device=dev)
-            ops.conv_fwd(x0, None, wp, coutp, bp, 2, 1, (0, 0, 0), out, (do_, ho, wo), stats=part,
-                         real=(spec.cin, spec.cout))
+            part = _conv_fwd_stats(want_stats, x0, None, wp, coutp, bp, 2, 1, (0, 0, 0), out, (do_, ho, wo), (spec.cin, spec.cout))
         elif (fp8 and spec.kind == "conv" and spec.ks == 3 and spec.stride == 1 and spec.pad == 1 and x1 is None
               and dtype == torch.bfloat16 and ops.conv_fp8_supported(x0, round_up(spec.cout, 32), out, (do_, ho, wo))):
             # BASELINE.json configs[4]: e4m3 operands (per-tensor scales) on the block-scaled MFMA, f32 accumulate, bf16 out
@@ -790,35 +737,24 @@ class ConvFn(Function):
             slot = spec.fp8_slot("x", dev)
             # (the packed batch enters both generator passes of a training step: cast once; never memoised outside training)
             x8 = fp8_operand(x0, slot, constant=torch.is_grad_enabled() and not x0.requires_grad and PackMemo.holds(x0))
-            q = (slot.use, amax_w)
-            bp = bias.detach() if bias is not None else None
-            if want_stats:
-                tiles, _ = ops.conv_num_tiles(x8, None, wp, coutp, 3, 1, (1, 1, 1), out, (do_, ho, wo), fp8=q)
-                part = torch.empty((tiles, 2, coutp), dtype=torch.float32, device=dev)
-            ops.conv_fwd(x8, None, wp, coutp, bp, 3, 1, (1, 1, 1), out, (do_, ho, wo), stats=part,
-                         real=(spec.cin, spec.cout), fp8=q)
+            part = _conv_fwd_stats(want_stats, x8, None, wp, coutp, bp, 3, 1, (1, 1, 1), out, (do_, ho, wo), (spec.cin, spec.cout),
+                                   fp8=(slot.use, amax_w))
         elif lazy_dx and spec.kind == "conv" and spec.ks == 1 and (pre := FusedFinal.take(x0, weight)) is not None:
             out = pre                          # computed by the launch that produced x0 (ops.normact_fwd, final=)
         elif spec.kind == "conv":
             wp, coutp, _ = spec.w_fwd(weight, dtype, c0 + c1)
-            bp = bias.detach() if bias is not None else None
-            pad3 = (spec.pad,) * 3
-            if want_stats:
-                tiles, _ = ops.conv_num_tiles(x0, x1, wp, coutp, spec.ks, spec.stride, pad3, out, (do_, ho, wo))
-                part = torch.empty((tiles, 2, coutp), dtype=torch.float32, device=dev)
-            ops.conv_fwd(x0, x1, wp, coutp, bp, spec.ks, spec.stride, pad3, out, (do_, ho, wo), stats=part,
-                         real=(spec.cin, spec.cout))
+            part = _conv_fwd_stats(want_stats, x0, x1, wp, coutp, bp, spec.ks, spec.stride, (spec.pad,) * 3, out, (do_, ho, wo),
+                                   (spec.cin, spec.cout))
         else:
             assert x1 is None and not want_stats
             if spec.cout % 64 == 0:
                 # the 8 parity classes folded into the column index of one 1x1x1 GEMM (8*Cout columns)
                 wp, coutp, _ = spec.w_deconv_fwd_all(weight, dtype, c0)
-                ops.conv_fwd(x0, None, wp, coutp, bias.detach() if bias is not None else None, 1, 1, (0, 0, 0), out, (di, hi, wi), os=2,
+                ops.conv_fwd(x0, None, wp, coutp, bp, 1, 1, (0, 0, 0), out, (di, hi, wi), os=2,
                              real=(spec.cin, 8 * spec.cout), cls_cout=spec.cout)
             else:
                 for cls in CLASSES8:
                     wp, coutp, _ = spec.w_deconv_fwd(weight, dtype, c0, cls)
-                    bp = bias.detach() if bias is not None else None
                     ops.conv_fwd(x0, None, wp, coutp, bp, 1, 1, (0, 0, 0), out, (di, hi, wi), os=2, ooff=cls,
                                  real=(spec.cin, spec.cout))
         ctx.save_for_backward(x0, x1, weight)
@@ -831,11 +767,7 @@ class ConvFn(Function):
         # a normalisation with batch/instance statistics follows: the mean subtraction cancels the bias,
         # so its gradient is identically zero and is returned as exact zeros (no reduction pass)
         ctx.zero_bias_grad = zero_bias_grad
-        if part is None:
-            part = torch.empty((0,), dtype=torch.float32, device=dev)
-        ctx.mark_non_differentiable(part)
-        ctx.set_materialize_grads(False)      # no zero tensor (+ fill launch) for the statistics output in every backward
-        return out, part
+        return _out_and_stats(ctx, out, part)
 
     @staticmethod
     @once_differentiable
@@ -871,20 +803,12 @@ class ConvFn(Function):
                   and ops.conv_fp8_supported(dz, round_up(c0 + c1, 32), dxc, (di, hi, wi))):
                 wp, coutp, _, amax_w = spec.w_dgrad8(weight, cg)
                 slot = spec.fp8_slot("g", dev)
-                dz8, q = fp8_operand(dz, slot), (slot.use, amax_w)
-                if want_sums:
-                    tiles, _ = ops.conv_num_tiles(dz8, None, wp, coutp, 3, 1, (1, 1, 1), dxc, (di, hi, wi), fp8=q)
-                    sums = torch.empty((tiles, 2, coutp), dtype=torch.float32, device=dev)
-                ops.conv_fwd(dz8, None, wp, coutp, None, 3, 1, (1, 1, 1), dxc, (di, hi, wi),
-                             real=(spec.cout, spec.cin), fp8=q, stats=sums)
+                sums = _conv_fwd_stats(want_sums, fp8_operand(dz, slot), None, wp, coutp, None, 3, 1, (1, 1, 1), dxc, (di, hi, wi),
+                                       (spec.cout, spec.cin), fp8=(slot.use, amax_w))
             elif spec.kind == "conv" and spec.stride == 1:
-                wp, coutp, _ = spec.w_dgrad_s1(weight, dtype, cg, c0 + c1)
-                pad3 = (k - 1 - spec.pad,) * 3
-                if want_sums:
-                    tiles, _ = ops.conv_num_tiles(dz, None, wp, coutp, k, 1, pad3, dxc, (di, hi, wi))
-                    sums = torch.empty((tiles, 2, coutp), dtype=torch.float32, device=dev)
-                ops.conv_fwd(dz, None, wp, coutp, None, k, 1, pad3, dxc, (di, hi, wi),
-                             real=(spec.cout, spec.cin), stats=sums)
+                wp, coutp, _ = spec.w_dgrad_s1(weight, dtype, cg)
+                sums = _conv_fwd_stats(want_sums, dz, None, wp, coutp, None, k, 1, (k - 1 - spec.pad,) * 3, dxc, (di, hi, wi),
+                                       (spec.cout, spec.cin))
             elif spec.kind == "conv":
                 if not (k == 4 and spec.stride == 2 and spec.pad == 1 and di % 2 == 0 and hi % 2 == 0 and wi % 2 == 0):
                     raise NotImplementedError("strided data gradient is implemented for k4 s2 p1 on even extents")
@@ -909,16 +833,8 @@ class ConvFn(Function):
             run_dgrad = False
         side = SideStream.enabled and n * do_ * ho * wo <= SideStream.max_rows
         if ctx.needs_input_grad[2]:
-            # gradient storage owned by the path (gradsink.GradBuckets): the kernel writes (or, for a second use of the
-            # layer in this backward pass, accumulates) straight into weight.grad and autograd gets None
             weight = ctx.weight_param
-            wsink = sink_of(weight)
-            acc = wsink is not None and not wsink.fresh(weight)
-            dwt = sink_grad(weight) if wsink is not None else torch.empty_like(weight, dtype=torch.float32)
-
-            defer = [] if (not side and DeferredReduce.wants(wsink, weight, acc)) else None
-            if defer is None and wsink is not None:
-                acc = not wsink.fresh(weight)              # (wants() may have flushed this parameter's first contribution)
+            wsink, dwt, acc, defer = _grad_target(weight, deferrable=not side)
 
             def wgrad():
                 if ctx.s2d_cp:
@@ -944,33 +860,23 @@ class ConvFn(Function):
                 SideStream.run(wgrad, x0, x1, dz)
             else:
                 wgrad()
-            if defer:
-                DeferredReduce.add(defer, wsink, weight)
-            elif wsink is not None:
-                wsink.written(weight)
-            else:
-                dw = dwt
+            dw = _grad_done(wsink, weight, dwt, defer)
         if ctx.has_bias and ctx.needs_input_grad[3]:
-            bsink = sink_of(ctx.bias_param)
-            if ctx.zero_bias_grad:
-                if bsink is not None:
-                    bsink.written(ctx.bias_param)          # its slice of the bucket is zero and nobody ever writes it
-                else:
-                    db = _cached_zeros(spec.cout, dev)
-            elif bsink is not None:
-                fresh = bsink.fresh(ctx.bias_param)
-                if carried is not None:
-                    ops.colsum_from_parts(carried[0], carried[1], sink_grad(ctx.bias_param), accumulate=not fresh)
-                elif side:
-                    SideStream.run(lambda: ops.colsum_into(dz, sink_grad(ctx.bias_param), accumulate=not fresh), dz)
-                else:
-                    ops.colsum_into(dz, sink_grad(ctx.bias_param), accumulate=not fresh)
-                bsink.written(ctx.bias_param)
-            elif carried is not None:
-                db = torch.empty((spec.cout,), dtype=torch.float32, device=dev)
-                ops.colsum_from_parts(carried[0], carried[1], db)
-            else:
+            bias = ctx.bias_param
+            bsink = sink_of(bias)
+            if ctx.zero_bias_grad:                  # (with a sink: its slice of the bucket is zero and nobody ever writes it)
+                db = _grad_done(bsink, bias, _cached_zeros(spec.cout, dev) if bsink is None else None)
+            elif bsink is None and carried is None:
                 db = ops.colsum(dz)[: spec.cout].contiguous()
+            else:
+                bsink, dbt, bacc, _ = _grad_target(bias)
+                if carried is not None:
+                    ops.colsum_from_parts(carried[0], carried[1], dbt, accumulate=bacc)
+                elif side:
+                    SideStream.run(lambda: ops.colsum_into(dz, dbt, accumulate=bacc), dz)
+                else:
+                    ops.colsum_into(dz, dbt, accumulate=bacc)
+                db = _grad_done(bsink, bias, dbt)
         if run_dgrad:
             dx0, dx1 = dgrad()
         return dx0, dx1, dw, db, None, None, None, None, None, None
@@ -978,7 +884,7 @@ class ConvFn(Function):
 
 class StepMemo:
     """Tensors computed once per training step and reused inside it, keyed by the objects they were computed from; emptied
-    at the start of every step like PackMemo (``DropoutState.advance``).  Holds the x-part of the PatchGAN's first block
+    at the start of every step like PackMemo (``begin_step``).  Holds the x-part of the PatchGAN's first block
     (SplitS2dConvFn): the same batch x and the same discriminator weights enter D in the generator phase and in both calls
     of the discriminator phase (src/model.py:172,184-186)."""
     _store = {}
@@ -999,6 +905,9 @@ class StepMemo:
     @classmethod
     def clear(cls):
         cls._store.clear()
+
+
+HandOver.per_step.append(StepMemo)
 
 
 class SplitS2dConvFn(Function):
@@ -1032,20 +941,12 @@ class SplitS2dConvFn(Function):
             StepMemo.put((sx, weight), tag, px)
         wpy, coutp, _ = spec.w_fwd_s2d_part(weight, dtype, cpy, cx, cy)
         out = ops.new_act(ny, *grid, cp, dtype, dev)
-        part = None
-        bp = bias.detach() if bias is not None else None
-        if want_stats:
-            tiles, _ = ops.conv_num_tiles(sy, None, wpy, coutp, 2, 1, (0, 0, 0), out, grid, addend=px)
-            part = torch.empty((tiles, 2, coutp), dtype=torch.float32, device=dev)
-        ops.conv_fwd(sy, None, wpy, coutp, bp, 2, 1, (0, 0, 0), out, grid, stats=part, addend=px, real=(cy, spec.cout))
+        part = _conv_fwd_stats(want_stats, sy, None, wpy, coutp, bias.detach() if bias is not None else None, 2, 1, (0, 0, 0), out, grid,
+                               (cy, spec.cout), addend=px)
         ctx.save_for_backward(sx, sy, weight)
         ctx.spec, ctx.cx, ctx.cy = spec, cx, cy
         ctx.bias_param, ctx.weight_param = bias, weight
-        if part is None:
-            part = torch.empty((0,), dtype=torch.float32, device=dev)
-        ctx.mark_non_differentiable(part)
-        ctx.set_materialize_grads(False)
-        return out, part
+        return _out_and_stats(ctx, out, part)
 
     @staticmethod
     @once_differentiable
@@ -1067,14 +968,9 @@ class SplitS2dConvFn(Function):
             ops.conv_fwd(dz, None, wp, coutp, None, 2, 1, (1, 1, 1), dsy, (di, hi, wi), real=(spec.cout, cy))
         if ctx.needs_input_grad[2]:
             weight = ctx.weight_param
-            wsink = sink_of(weight)
-            acc = wsink is not None and not wsink.fresh(weight)
-            dwt = sink_grad(weight) if wsink is not None else torch.empty_like(weight, dtype=torch.float32)
+            wsink, dwt, acc, defer = _grad_target(weight, deferrable=True)     # (x- and y-part: disjoint channel slices of dw)
             geo = (spec.cin * k ** 3, k ** 3, (k * k, k, 1), (0, 0, 0), (2, 2, 2))
             nx = sx.shape[0]
-            defer = [] if DeferredReduce.wants(wsink, weight, acc) else None   # (x- and y-part: disjoint channel slices of dw)
-            if defer is None and wsink is not None:
-                acc = not wsink.fresh(weight)
             if ny == 2 * nx and SplitS2dConvFn.sum_pair_gradients:
                 # both halves of a stacked pair saw the SAME x: x (*) dz_a + x (*) dz_b = x (*) (dz_a + dz_b) -- half the x-part's
                 # weight-gradient work for one pass over the two gradients (the sum is formed in f32 and rounded to bf16 once)
@@ -1085,19 +981,14 @@ class SplitS2dConvFn(Function):
                                defer=defer)
             ops.conv_wgrad(sy, None, dz, grid, 1, (0, 0, 0), 2, 1, (0, 0, 0), dwt, spec.cout, cy, *geo, s2d_cp=cpy, accumulate=acc,
                            dw_offset=cx * k ** 3, defer=defer)
-            if defer:
-                DeferredReduce.add(defer, wsink, weight)
-            elif wsink is not None:
-                wsink.written(weight)
-            else:
-                dw = dwt
+            dw = _grad_done(wsink, weight, dwt, defer)
         if ctx.bias_param is not None and ctx.needs_input_grad[3]:
-            bsink = sink_of(ctx.bias_param)
-            if bsink is not None:
-                ops.colsum_into(dz, sink_grad(ctx.bias_param), accumulate=not bsink.fresh(ctx.bias_param))
-                bsink.written(ctx.bias_param)
-            else:
+            if sink_of(ctx.bias_param) is None:
                 db = ops.colsum(dz)[: spec.cout].contiguous()
+            else:
+                bsink, dbt, acc, _ = _grad_target(ctx.bias_param)
+                ops.colsum_into(dz, dbt, accumulate=acc)
+                db = _grad_done(bsink, ctx.bias_param, dbt)
         return None, dsy, dw, db, None, None, None, None
 
 
@@ -1161,20 +1052,12 @@ class UpCatConvFn(Function):
         ops.conv_fwd(x_e, None, wps, coutp, None, 3, 1, (1, 1, 1), p_skip, (D, H, W), real=(ce, co))
         out = ops.new_act(n, D, H, W, co, dtype, dev)
         grid = (D // 2, H // 2, W // 2)
-        part = None
-        if want_stats:
-            tiles, _ = ops.conv_num_tiles(x_low, None, wp, 8 * co, 2, 1, (0, 0, 0), out, grid, addend=p_skip, d2s=True)
-            part = torch.empty((tiles, 2, co), dtype=torch.float32, device=dev)
-        ops.conv_fwd(x_low, None, wp, 8 * co, biasp, 2, 1, (0, 0, 0), out, grid, stats=part, addend=p_skip, d2s=True, delta=delta,
-                     real=(cl, 8 * co))
+        part = _conv_fwd_stats(want_stats, x_low, None, wp, 8 * co, biasp, 2, 1, (0, 0, 0), out, grid, (cl, 8 * co), cols=co, delta=delta,
+                               addend=p_skip, d2s=True)
         ctx.save_for_backward(x_e, x_low, wd, wc, bd)
         ctx.spec_c, ctx.tables = spec_c, tables
         ctx.params = (wd, bd, wc, bc)
-        if part is None:
-            part = torch.empty((0,), dtype=torch.float32, device=dev)
-        ctx.mark_non_differentiable(part)
-        ctx.set_materialize_grads(False)
-        return out, part
+        return _out_and_stats(ctx, out, part)
 
     @staticmethod
     @once_differentiable
@@ -1202,15 +1085,9 @@ class UpCatConvFn(Function):
             ops.conv_fwd(sg, None, wpk[0], wpk[1], None, 2, 1, (0, 0, 0), dx_low, grid, real=(co, cl))
         if need_w:
             wd_p, bd_p, wc_p, bc_p = ctx.params
-
-            def target(p):
-                sink = sink_of(p)
-                if sink is not None:
-                    return sink, sink_grad(p), not sink.fresh(p)
-                return None, torch.empty_like(p, dtype=torch.float32), False
-            sk_c, dwc_t, acc_c = target(wc_p)
-            sk_d, dwd_t, acc_d = target(wd_p)
-            sk_b, dbd_t, acc_b = target(bd_p)
+            sk_c, dwc_t, acc_c, _ = _grad_target(wc_p)
+            sk_d, dwd_t, acc_d, _ = _grad_target(wd_p)
+            sk_b, dbd_t, acc_b, _ = _grad_target(bd_p)
             assert acc_c == acc_d == acc_b, "the UpCat block's parameters are used together"
             ops.conv_wgrad(x_e, None, dz, (D, H, W), 1, (0, 0, 0), 3, 1, (1, 1, 1), dwc_t, co, ce, (ce + cu) * 27, 27, (9, 3, 1),
                            (0, 0, 0), (1, 1, 1), accumulate=acc_c)
@@ -1219,19 +1096,11 @@ class UpCatConvFn(Function):
                            s2d_cp=co)
             esum = ops.border_sums(dz, co)
             ops.upcat_chain(dk4, wd.detach(), wc.detach(), bd.detach(), esum, ce, dwd_t, dwc_t, dbd_t, acc_c)
-            for sk, p in ((sk_c, wc_p), (sk_d, wd_p), (sk_b, bd_p)):
-                if sk is not None:
-                    sk.written(p)
-            dwc = None if sk_c is not None else dwc_t
-            dwd = None if sk_d is not None else dwd_t
-            dbd = None if sk_b is not None else dbd_t
+            dwc, dwd, dbd = _grad_done(sk_c, wc_p, dwc_t), _grad_done(sk_d, wd_p, dwd_t), _grad_done(sk_b, bd_p, dbd_t)
             if bc_p is not None and ctx.needs_input_grad[5]:
                 # a normalisation follows: the mean subtraction cancels the convolution's bias, its gradient is exactly zero
                 bsink = sink_of(bc_p)
-                if bsink is not None:
-                    bsink.written(bc_p)
-                else:
-                    dbc = _cached_zeros(co, dev)
+                dbc = _grad_done(bsink, bc_p, _cached_zeros(co, dev) if bsink is None else None)
         return dx_e, dx_low, dwd, dbd, dwc, dbc, None, None, None
 
 
@@ -1245,7 +1114,7 @@ class NormCfg:
 class DropoutState:
     """Dropout randomness without host involvement per launch: one 64-bit step counter per device in
     device memory (seeded from torch's CPU generator, so torch.manual_seed governs it) plus a per-call
-    salt.  ``advance()`` (once per training step) bumps the counter ON THE DEVICE, so a step captured
+    salt.  ``advance()`` (once per training step: ``begin_step``) bumps the counter ON THE DEVICE, so a step captured
     in a hipGraph draws fresh masks at every replay."""
     _base = {}
     _salt = 0
@@ -1267,19 +1136,23 @@ class DropoutState:
     def advance(cls, device):
         cls.base(device).add_(1)
         cls._salt = 0
-        PackMemo.clear()                    # a new training step: constant inputs are packed afresh
-        StepMemo.clear()
-        ColSumSide.clear()
-        LazyDx.clear()
-        LazyPool.clear()
-        PoolSide.clear()
-        FusedFinal.clear()
-        Fp8Scales.advance(device)           # ... and the e4m3 scales gathered in the last step come into use
 
     @classmethod
     def reset(cls):
         cls._base.clear()
         cls._salt = 0
+
+
+def begin_step(device):
+    """A training step begins: fresh dropout masks, constant inputs are packed afresh, nothing of the last step is left in a
+    hand-over table, and the e4m3 scales gathered in the last step come into use."""
+    DropoutState.advance(device)
+    for table in HandOver.per_step:
+        table.clear()
+    Fp8Scales.advance(device)
+
+
+NORMACT_INPUTS = 17         # NormActFn.forward's arguments after ctx: its backward returns one entry for each
 
 
 class NormActFn(Function):
@@ -1305,35 +1178,17 @@ class NormActFn(Function):
         assert n % groups == 0
         mean = rstd = None
         batch_stats = False
-        ctx.small = False
         ctx.emit8_bwd = emit8_bwd if (emit8_bwd is not None and emit8_bwd.primed and not small and not s2d_out) else None
         if emit8 is not None and not (emit8.primed and not small and not s2d_out and z.dtype == torch.bfloat16 and c == 32):
             emit8 = None
-        if small and cfg.kind != "none" and use_batch:
-            # small tensor (low U-Net levels, last PatchGAN blocks): statistics, norm, dropout and activation in ONE launch
-            if rows // groups <= 1:
-                raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
-            gp = gamma.detach() if gamma is not None else None
-            bp = beta.detach() if beta is not None else None
-            p = cfg.p if training else 0.0
-            seed = DropoutState.next_salt() if p > 0.0 else 0
-            seed_t = DropoutState.base(z.device) if p > 0.0 else None
-            upd = cfg.kind == "batch" and training and running_mean is not None
-            out = _new_s2d(ops.s2d_shape(n, d, h, w, c), z.dtype, z.device) if s2d_out else None
-            a, mean, rstd = ops.normact_small_fwd(z, groups, gp, bp, cfg.eps, cfg.slope, p, seed, seed_t,
-                                                  running_mean if upd else None, running_var if upd else None, cfg.momentum,
-                                                  batches_tracked if upd else None, out=out, s2d=s2d_out)
-            ctx.small = True
-            ctx.s2d_out = s2d_out
-            ctx.seed_t = seed_t
-            ctx.affine_params = (gamma, beta)
-            ctx.save_for_backward(z, mean, rstd, gp, bp)
-            ctx.meta = (groups, cfg.slope, p, seed, True, gamma.numel() if gamma is not None else 0)
-            return a
-        if cfg.kind != "none":
+        small = small and cfg.kind != "none" and use_batch      # statistics, norm, dropout and activation in ONE launch
+        upd = cfg.kind == "batch" and training and running_mean is not None
+        if cfg.kind != "none" and use_batch and rows // groups <= 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
+        if small:
+            batch_stats = True
+        elif cfg.kind != "none":
             if use_batch:
-                if rows // groups <= 1:
-                    raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
                 if part is not None and part.numel() > 0:
                     assert part.shape[2] == c, "fused statistics need coutp == padded channels"
                     ppg = part.shape[0] // groups
@@ -1341,7 +1196,6 @@ class NormActFn(Function):
                 else:
                     part, ppg = ops.channel_stats(z, groups)
                     shift = None
-                upd = cfg.kind == "batch" and training and running_mean is not None
                 n_real = running_mean.numel() if upd else (shift.numel() if shift is not None else 0)
                 mean, rstd = ops.norm_finalize(part, ppg, groups, c, rows // groups, shift, cfg.eps,
                                                running_mean if upd else None, running_var if upd else None,
@@ -1356,7 +1210,13 @@ class NormActFn(Function):
         p = cfg.p if training else 0.0
         seed = DropoutState.next_salt() if p > 0.0 else 0
         seed_t = DropoutState.base(z.device) if p > 0.0 else None
-        if s2d_out:
+        if small:
+            # small tensor (low U-Net levels, last PatchGAN blocks)
+            out = _new_s2d(ops.s2d_shape(n, d, h, w, c), z.dtype, z.device) if s2d_out else None
+            a, mean, rstd = ops.normact_small_fwd(z, groups, gp, bp, cfg.eps, cfg.slope, p, seed, seed_t,
+                                                  running_mean if upd else None, running_var if upd else None, cfg.momentum,
+                                                  batches_tracked if upd else None, out=out, s2d=s2d_out)
+        elif s2d_out:
             out = _new_s2d(ops.s2d_shape(n, d, h, w, c), z.dtype, z.device)
             a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, out=out, s2d=True, seed_t=seed_t)
         elif emit8 is not None:
@@ -1371,7 +1231,7 @@ class NormActFn(Function):
             y = ops.new_act(n, d, h, w, round_up(fw.shape[0], 16), z.dtype, z.device)
             a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t,
                                 final=(fw.detach(), fb.detach() if fb is not None else None, y), skip_a=skip_a)
-            FusedFinal.put(a, y, fw)
+            FusedFinal.put(a, y, fw, fw._version)
         elif (pool_after and PoolSide.enabled and not s2d_out and emit8 is None and d % 2 == 0 and h % 2 == 0 and w % 2 == 0
               and (rows // groups) % (d * h * w) == 0):
             # the activation's only consumer is SkipPoolFn (nn.Down.forward_skip): its MaxPool3d(2) in this launch (PoolSide)
@@ -1379,6 +1239,7 @@ class NormActFn(Function):
             PoolSide.put(a, py, pidx)
         else:
             a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t)
+        ctx.small = small
         ctx.s2d_out = s2d_out
         ctx.seed_t = seed_t
         ctx.affine_params = (gamma, beta)
@@ -1404,45 +1265,29 @@ class NormActFn(Function):
                 da = ops.maxpool2_bwd(lp[0], lp[1], lp[3], lp[4])     # these kernels read a materialised gradient
             else:
                 pool, da = (lp[2], lp[3]), lp[4]
-        want_affine = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        need_g, need_b = ctx.needs_input_grad[2:4]
+        want_affine = need_g or need_b
         gamma_p, beta_p = ctx.affine_params
-        sink = sink_of(gamma_p) if (ctx.needs_input_grad[2] and ctx.needs_input_grad[3] and mean is not None) else None
-        slot8 = ctx.emit8_bwd if (not ctx.small and z.dtype == torch.bfloat16 and z.shape[4] == 32) else None
-        q8 = (torch.empty(z.shape, dtype=torch.uint8, device=z.device), slot8.use, slot8.next) if slot8 is not None else None
-
-        def done(dz):
+        kw = dict(s2d=ctx.s2d_out, seed_t=ctx.seed_t)
+        sink = sink_of(gamma_p) if (need_g and need_b and mean is not None and sink_of(beta_p) is sink_of(gamma_p)) else None
+        if sink is not None:
+            # both affine gradients straight into the parameters' .grad storage (gradsink.py)
+            _, dg_t, acc, _ = _grad_target(gamma_p)
+            kw.update(affine_into=(dg_t, sink_grad(beta_p)), accumulate=acc)
+        if ctx.small:
+            dz, dgamma, dbeta = ops.normact_small_bwd(z, da, groups, mean, rstd, gp, bp, slope, p, seed, batch_stats,
+                                                      want_affine=want_affine, **kw)
+        else:
+            slot8 = ctx.emit8_bwd if (z.dtype == torch.bfloat16 and z.shape[4] == 32) else None
+            q8 = (torch.empty(z.shape, dtype=torch.uint8, device=z.device), slot8.use, slot8.next) if slot8 is not None else None
+            dz, dgamma, dbeta = ops.normact_bwd(z, da, groups, mean, rstd, gp, bp, slope, p, seed, batch_stats,
+                                                want_affine and mean is not None, q8=q8, implicit=lazy, pool=pool, **kw)
             if q8 is not None:
                 slot8.touched = True
                 Fp8Side.put(dz, q8[0])
-            return dz
-        if ctx.small:
-            none11 = (None,) * 16
-            if sink is not None and sink_of(beta_p) is sink:
-                dz, _, _ = ops.normact_small_bwd(z, da, groups, mean, rstd, gp, bp, slope, p, seed, batch_stats, s2d=ctx.s2d_out,
-                                                 seed_t=ctx.seed_t, affine_into=(sink_grad(gamma_p), sink_grad(beta_p)),
-                                                 accumulate=not sink.fresh(gamma_p))
-                sink.written(gamma_p)
-                sink.written(beta_p)
-                return (dz,) + none11
-            dz, dgamma, dbeta = ops.normact_small_bwd(z, da, groups, mean, rstd, gp, bp, slope, p, seed, batch_stats,
-                                                      s2d=ctx.s2d_out, seed_t=ctx.seed_t, want_affine=want_affine)
-            dg = dgamma[:nch].contiguous() if (dgamma is not None and ctx.needs_input_grad[2]) else None
-            dbt = dbeta[:nch].contiguous() if (dbeta is not None and ctx.needs_input_grad[3]) else None
-            return (dz, None, dg, dbt) + (None,) * 13
-        if sink is not None and sink_of(beta_p) is sink:
-            # both affine gradients straight into the parameters' .grad storage (gradsink.py)
-            dz, _, _ = ops.normact_bwd(z, da, groups, mean, rstd, gp, bp, slope, p, seed, batch_stats, True,
-                                       s2d=ctx.s2d_out, seed_t=ctx.seed_t, affine_into=(sink_grad(gamma_p), sink_grad(beta_p)),
-                                       accumulate=not sink.fresh(gamma_p), q8=q8, implicit=lazy, pool=pool)
-            sink.written(gamma_p)
-            sink.written(beta_p)
-            return (done(dz),) + (None,) * 16
-        dz, dgamma, dbeta = ops.normact_bwd(z, da, groups, mean, rstd, gp, bp, slope, p, seed, batch_stats,
-                                            want_affine and mean is not None, s2d=ctx.s2d_out, seed_t=ctx.seed_t, q8=q8,
-                                            implicit=lazy, pool=pool)
-        dg = dgamma[:nch].contiguous() if (dgamma is not None and ctx.needs_input_grad[2]) else None
-        dbt = dbeta[:nch].contiguous() if (dbeta is not None and ctx.needs_input_grad[3]) else None
-        return (done(dz), None, dg, dbt) + (None,) * 13
+        dg = _grad_done(sink, gamma_p, dgamma[:nch].contiguous() if (dgamma is not None and need_g) else None)
+        dbt = _grad_done(sink, beta_p, dbeta[:nch].contiguous() if (dbeta is not None and need_b) else None)
+        return (dz, None, dg, dbt) + (None,) * (NORMACT_INPUTS - 4)
 
 
 # ====================================================================================== pool / loss

@@ -282,8 +282,8 @@ class bSSFPToDWITensorModel(nn.Module):
         """toggle(gen_opt) -> _gen_step -> manual_backward          (src/model.py:264-268)"""
         x, y = self.unpack_batch(batch)
         if x.is_cuda:
-            from .functional import DropoutState, StageBoundary
-            DropoutState.advance(x.device)
+            from .functional import StageBoundary, begin_step
+            begin_step(x.device)
             if self.enable_grad_sinks():
                 self.sinks_gen.begin_phase(1)
             if staged:
@@ -352,8 +352,8 @@ class bSSFPToDWITensorModel(nn.Module):
         parameters), so that an attached model averages its gradients over the ranks here as well."""
         x, y = self.unpack_batch(batch)
         if x.is_cuda:
-            from .functional import DropoutState
-            DropoutState.advance(x.device)
+            from .functional import begin_step
+            begin_step(x.device)
             if self.enable_grad_sinks():
                 self.sinks_gen.begin_phase(1)
         loss = self._l1(self.gen(x), y)
