@@ -168,6 +168,8 @@ int64_t mi355_conv_workspace_bytes(const mi355_conv_desc* d);
 /* which kernel instance mi355_conv_fwd() will launch for this descriptor (for profiling tools):
  * 10000*ks + 1000*halo + 100*tile_shape + 10*voxel_subtiles_per_wave + cout_subtiles_per_wave, <0 on error */
 int mi355_conv_plan_id(const mi355_conv_desc* d);
+/* output planes per workgroup segment of the marching plans (tile shapes 10, 11, 14), 0 for every other plan, <0 on error */
+int mi355_conv_plan_seg_len(const mi355_conv_desc* d);
 /* number of spatial tiles (= rows of stats_part) and tiles per sample (0 if tiles span samples) */
 int mi355_conv_num_tiles(const mi355_conv_desc* d, int32_t* tiles, int32_t* tiles_per_sample);
 

@@ -110,6 +110,7 @@ _SIGNATURES = {
     "mi355_conv_fwd": (C.c_int, [C.POINTER(ConvDesc), _vp]),
     "mi355_conv_workspace_bytes": (_i64, [C.POINTER(ConvDesc)]),
     "mi355_conv_plan_id": (C.c_int, [C.POINTER(ConvDesc)]),
+    "mi355_conv_plan_seg_len": (C.c_int, [C.POINTER(ConvDesc)]),
     "mi355_conv_num_tiles": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(_i32), C.POINTER(_i32)]),
     "mi355_conv_wgrad_workspace": (_i64, [C.POINTER(WgradDesc)]),
     "mi355_conv_wgrad_plan_kind": (C.c_int, [C.POINTER(WgradDesc)]),

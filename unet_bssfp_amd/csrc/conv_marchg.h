@@ -25,6 +25,18 @@
 // block read a weight slot whose copy had not landed (plausible-looking wrong sums, run-to-run differences at 128^3 only).
 // Loads retire in order among themselves, which is all the count relies on; a pending store only makes a wait longer.
 //
+// LIVE BLOCKS ONLY.  The workgroup's output planes are its d-segment [d0, d1); block kd of input plane p feeds output plane
+// p + 1 - kd, so plane d0 - 1 has only kd = 0 (live mask 001), plane d0 kd = 1, 0 (011), the interior all three (111), plane
+// d1 - 1 kd = 2, 1 (110), plane d1 kd = 2 (100), and the middle plane of a one-plane segment kd = 1 (010): at 32^3 the planner's
+// segments are ONE plane long (2/3 of the block slots dead), at 64^3 four (1/3).  unit() is peeled on the mask at compile time
+// and holds nothing for a dead slot -- no barrier, no wait, no ticket, no zero-filled copy.  The copies are spread over the
+// live blocks: each requests the weights of the live block after next in program order (a scalar cursor; static in a 111
+// unit), the unit's live blocks but the last share the next plane unit, and a unit of ONE live block issues the plane copies
+// first and the weight copies behind them, so that its wait can leave the weight copies alone in flight.  Every wait count
+// is a compile-time constant of the variant.  The plane sequence is straight-line code per segment length (1, 2, >= 3 planes),
+// chosen before any accumulator is live.  The order in which contributions reach an output plane is that of the version
+// that ran the dead slots: results are bit-identical.
+//
 // ROWS = 4: 16 x 32 footprints (128^3, 64^3: enough footprints x d-segments to fill 256 CUs); ROWS = 2: 8 x 32 footprints for
 // the 32^3 level (twice the workgroups, 1.17 instead of 0.75 LDS reads per MFMA).
 #pragma once
@@ -126,14 +138,12 @@ __global__ __launch_bounds__(256, 1) void conv_marchg_kernel(const ConvArgs a, c
   // [lane half][row] x 16 B; row rho holds output channel pi(rho) (conv_march.h: a lane ends up with 16 contiguous channels)
   const int wrow = 16 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3);
   const int wsrc = ((co_base + wrow) * 2 + h) * 16;
-  // (p: the input plane of the block; a block whose output plane lies outside the segment does not run and gets zeros)
-  auto load_w = [&](int p, int g, int kd, int slot) __attribute__((always_inline)) {
+  auto load_w = [&](int g, int kd, int slot) __attribute__((always_inline)) {
     char* dst = wl + slot * Cfg::WUNIT + wave * 1024;
-    const bool runs = p <= d1 && (kd == 2 ? p - 1 >= d0 : (kd == 1 ? (p >= d0 && p < d1) : p + 1 < d1));
 #pragma unroll
     for (int i = 0; i < NWI; ++i) {
       const int j = i * 4 + wave, c = j >= 9 ? 1 : 0, t9 = j - 9 * c;  // wave-uniform
-      const bool ok = j < 18 && runs;
+      const bool ok = j < 18;                                          // (the slot's two pad blocks: zeros)
       const int soff = ok ? (((2 * g + c) * 27 + kd * 9 + t9) * a.coutp) * 32 : 0;
 #ifndef MG_DIAG_NO_DMA_W
       dma_lds_b128(rsw, dst + i * 4096, ok ? wsrc : (int)0x80000000, soff);
@@ -165,12 +175,9 @@ __global__ __launch_bounds__(256, 1) void conv_marchg_kernel(const ConvArgs a, c
     asm volatile("" :: "v"(voff), "s"(q.soff));
 #endif
   };
-  auto w_runs = [&](int p, int kd) __attribute__((always_inline)) {
-    return p <= d1 && (kd == 2 ? p - 1 >= d0 : (kd == 1 ? (p >= d0 && p < d1) : p + 1 < d1));
-  };
-  auto w_ticket = [&](bool runs, int g, int kd, int slot, int i) __attribute__((always_inline)) {
+  auto w_ticket = [&](int g, int kd, int slot, int i) __attribute__((always_inline)) {
     const int j = i * 4 + wave, c = j >= 9 ? 1 : 0, t9 = j - 9 * c;    // wave-uniform
-    const bool ok = j < 18 && runs;
+    const bool ok = j < 18;
     const int soff = ok ? (((2 * g + c) * 27 + kd * 9 + t9) * a.coutp) * 32 : 0;
 #ifndef MG_DIAG_NO_DMA_W
     dma_lds_b128(rsw, wl + slot * Cfg::WUNIT + wave * 1024 + i * 4096, ok ? wsrc : (int)0x80000000, soff);
@@ -267,123 +274,231 @@ __global__ __launch_bounds__(256, 1) void conv_marchg_kernel(const ConvArgs a, c
   };
   // between(gi): called after group gi's MFMAs, fenced (nothing is scheduled across): the block's copy tickets;
   // within(gi): called in front of group gi's MFMAs, unfenced: VALU work the scheduler may spread under the MFMAs (epilogue rows)
-  auto block = [&](const bool run, const char* apl, const char* wpl, f32x16 (&s)[ROWS], auto within, auto between) __attribute__((always_inline)) {
-    if (run) {
-      Group g[2];
-      load_group(g[0], apl, wpl, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);
+  auto block = [&](const char* apl, const char* wpl, f32x16 (&s)[ROWS], auto within, auto between) __attribute__((always_inline)) {
+    Group g[2];
+    load_group(g[0], apl, wpl, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);
 #pragma unroll
-      for (int gi = 0; gi < 6; ++gi) {
-        within(gi);
-        if (gi + 1 < 6) load_group(g[(gi + 1) & 1], apl, wpl, gi + 1);
-        mma_group(g[gi & 1], s);
+    for (int gi = 0; gi < 6; ++gi) {
+      within(gi);
+      if (gi + 1 < 6) load_group(g[(gi + 1) & 1], apl, wpl, gi + 1);
+      mma_group(g[gi & 1], s);
 #pragma unroll
-        for (int k = 0; k < NMM; ++k) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if (gi + 1 < 6) {
-            const int nr = ((k + 1) * NRD) / NMM - (k * NRD) / NMM;      // the next group's NRD reads spread over this group's MFMAs
-            if (nr == 1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            else if (nr == 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-          }
+      for (int k = 0; k < NMM; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        if (gi + 1 < 6) {
+          const int nr = ((k + 1) * NRD) / NMM - (k * NRD) / NMM;      // the next group's NRD reads spread over this group's MFMAs
+          if (nr == 1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          else if (nr == 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         }
-        __builtin_amdgcn_sched_barrier(0);
-        between(gi);
-        __builtin_amdgcn_sched_barrier(0);
       }
-    } else {                                   // a block whose output plane lies outside the segment: its copies and epilogue rows only
-#pragma unroll
-      for (int gi = 0; gi < 6; ++gi) { within(gi); between(gi); }
+      __builtin_amdgcn_sched_barrier(0);
+      between(gi);
+      __builtin_amdgcn_sched_barrier(0);
     }
   };
 
-  // ---- unit (p, g): blocks kd = 2, 1, 0 on output planes p - 1 (s_m1), p (s_0), p + 1 (s_p1).  Weight slot of kd block k
-  //      is 2 - kd (fixed: a unit is three blocks and the ring has three slots); at the start of a block the weights of the
-  //      block after next are requested, at the start of a unit the next plane unit.
-  //      Counted waits: at the end of a block everything issued BEFORE this block must have landed.
+  // ---- live blocks.  Block kd of input plane p feeds output plane p + 1 - kd and exists only if that plane lies in
+  //      [d0, d1): the live kd of a plane are the range [kd_lo(p), kd_hi(p)], the same for all its groups.  Program order:
+  //      planes ascending, groups ascending, kd descending.
+  struct Blk { int p, g, kd; };
+  auto kd_lo = [&](int p) __attribute__((always_inline)) { return max(0, p + 2 - d1); };
+  auto kd_hi = [&](int p) __attribute__((always_inline)) { return min(2, p + 1 - d0); };
+  auto blk_next = [&](const Blk b) __attribute__((always_inline)) {    // wave-uniform selects: scalar code, no branch (a
+    const bool same_unit = b.kd > kd_lo(b.p);                          // join between two blocks would cross live accumulators)
+    const bool same_plane = same_unit || b.g + 1 < ng;
+    Blk n;
+    n.p = same_plane ? b.p : b.p + 1;
+    n.g = same_unit ? b.g : (same_plane ? b.g + 1 : 0);
+    n.kd = same_unit ? b.kd - 1 : kd_hi(n.p);
+    // (pinned to scalar registers: the copies take them as the "s" operands of inline assembly)
+    n.p = __builtin_amdgcn_readfirstlane(n.p);
+    n.g = __builtin_amdgcn_readfirstlane(n.g);
+    n.kd = __builtin_amdgcn_readfirstlane(n.kd);
+    return n;
+  };
+
+  // ---- unit (p, g) of a plane with live mask MASK (bit kd): its live blocks, kd descending, on the output planes p - 1
+  //      (s_m1, kd = 2), p (s_0), p + 1 (s_p1).  The weight ring has three slots and every live block requests the weights
+  //      of the live block after next into the slot the previous live block read (that block's barrier has been passed);
+  //      the unit's live blocks but the last share the copies of the next plane unit.  Counted waits: at the end of a block
+  //      everything issued BEFORE this block must have landed -- dma_wait_but<copies this block issued>.  A unit with ONE
+  //      live block has no earlier block for the plane copies: they are issued first, the weight copies behind them, and
+  //      the wait leaves the weight copies alone in flight (loads retire in order).
+  //      MASK = 111: three blocks a unit, and the blocks in front of the first such plane are 3 ng (planes 001 and 011), so
+  //      block kd sits in slot 2 - kd and its requests are static: this unit's kd = 0, the next unit's kd = 2 and kd = 1.
+  //      The other masks take the slot from the running block count (`ring`) and the request from a cursor that stays two
+  //      live blocks ahead (`rq`).
   int u = 0;                                                           // units done (act slot = u & 1)
+  int ring = 0;                                                        // live blocks done, mod 3 (weight slot of the current block)
+  Blk rq;                                                              // the live block after next
   // LAST (compile time): this is the plane's last group -- its kd = 2 block completes output plane p - 1, whose epilogue runs
-  // under the kd = 1 / kd = 0 blocks and leaves the register set zeroed for its next role (the plane after next's kd = 0).
-  // The g loop is peeled instead of branching on g: with the epilogue inside a run-time diamond hipcc spilled 224 registers.
-  constexpr int NA0 = (NI + 1) / 2, NA1 = NI - NA0;                    // plane-unit copies issued in the kd = 2 / kd = 1 block
-  // copy tickets of a block: NW weight copies and NA plane copies alternate (W0 A0 W1 A1 ...), ticket t goes behind fragment
-  // group t * 6 / NT -- at most two copies between two groups
-  auto tickets = [&](const int gi, const int na, auto wt, auto at) __attribute__((always_inline)) {
-    const int nt = NWI + na, pairs = na < NWI ? na : NWI;
+  // under the kd = 1 block (after the block where the plane has none) and leaves the register set zeroed for its next role
+  // (the plane after next's kd = 0).  The g loop is peeled instead of branching on g: with the epilogue inside a run-time
+  // diamond hipcc spilled 224 registers.
+  // TAIL (compile time; the segment's last plane only, mask 100): 0 = a block after next and a next unit exist, 1 = no
+  // block after next (no weight request), 2 = the segment's last unit (no request at all).
+  constexpr int NA0 = (NI + 1) / 2, NA1 = NI - NA0;                    // plane-unit copies in the first / second block of three
+  // copy tickets of a block: nw weight copies and na plane copies alternate (W0 A0 W1 A1 ...), ticket t goes behind fragment
+  // group t * 6 / nt -- at most three copies between two groups (two in a unit of three blocks)
+  auto tickets = [&](const int gi, const int nw, const int na, auto wt, auto at) __attribute__((always_inline)) {
+    const int nt = nw + na, pairs = na < nw ? na : nw;
 #pragma unroll
     for (int t = 0; t < NWI + NI; ++t) {
       if (t >= nt || (t * 6) / nt != gi) continue;
       if (t < 2 * pairs) { if (t % 2 == 0) wt(t / 2); else at(t / 2); }
-      else if (na < NWI) wt(pairs + t - 2 * pairs);
+      else if (na < nw) wt(pairs + t - 2 * pairs);
       else at(pairs + t - 2 * pairs);
     }
   };
-  auto unit = [&](auto last_tag, int p, int g, f32x16 (&s_m1)[ROWS], f32x16 (&s_0)[ROWS], f32x16 (&s_p1)[ROWS]) __attribute__((always_inline)) {
+  // ... of a unit's ONLY block: the plane copies first, two behind each group from the start (they must land within this
+  // block), every weight copy behind the last of them
+  static_assert((NI + 1) / 2 <= 5, "the plane copies of a one-block unit must leave a fragment group for the weight copies");
+  auto tickets_act_first = [&](const int gi, const int nw, const int na, auto wt, auto at) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+      if (i < na && i / 2 == gi) at(i);
+#pragma unroll
+    for (int i = 0; i < NWI; ++i)
+      if (i < nw && ((NI + 1) / 2 + i / 2 < 5 ? (NI + 1) / 2 + i / 2 : 5) == gi) wt(i);
+  };
+  auto unit = [&](auto mask_tag, auto last_tag, auto tail_tag, int p, int g, f32x16 (&s_m1)[ROWS], f32x16 (&s_0)[ROWS], f32x16 (&s_p1)[ROWS]) __attribute__((always_inline)) {
+    constexpr int MASK = decltype(mask_tag)::value, TAIL = decltype(tail_tag)::value;
     constexpr bool LAST = decltype(last_tag)::value;
+    constexpr int NB = ((MASK >> 2) & 1) + ((MASK >> 1) & 1) + (MASK & 1);
+    static_assert(NB >= 1 && MASK != 5 && (TAIL == 0 || MASK == 4), "live kd blocks are a range; only the last plane has a tail");
     const char* apl = smem + (u & 1) * Cfg::PLANE;
     const int gn = LAST ? 0 : g + 1, pn = LAST ? p + 1 : p;             // the next unit
-    // (past the segment's last unit the copies turn into zero-fills: same instruction count for the counted waits)
-    const ActSrc nx = act_src(pn, pn <= d1 ? gn : ng);
+    const ActSrc nx = act_src(pn, gn);
     const int nslot = (u + 1) & 1;
     int e[NI];
+    if constexpr (TAIL < 2) {
 #pragma unroll
-    for (int i = 0; i < NI; ++i) e[i] = vtab[i * 256];
-    const bool do2 = p - 1 >= d0 && p <= d1, do1 = p >= d0 && p < d1, do0 = p + 1 < d1;
-    const bool r0 = w_runs(p, 0), r2n = w_runs(pn, 2), r1n = w_runs(pn, 1);
+      for (int i = 0; i < NI; ++i) e[i] = vtab[i * 256];
+    }
+    // the J-th live block of the unit, weights of kd block KD
+    auto live = [&](auto j_tag, auto kd_tag, f32x16 (&s)[ROWS], auto within) __attribute__((always_inline)) {
+      constexpr int J = decltype(j_tag)::value, KD = decltype(kd_tag)::value;
+      constexpr int NW = TAIL < 1 ? NWI : 0;
+      constexpr int NA = TAIL == 2 ? 0 : NB == 3 ? (J == 0 ? NA0 : J == 1 ? NA1 : 0) : (J == 0 ? NI : 0);
+      constexpr int A0 = (NB == 3 && J == 1) ? NA0 : 0;                 // the first plane copy of this block
+      const int slot = MASK == 7 ? 2 - KD : ring;
+      const int rslot = slot == 0 ? 2 : slot - 1;
+      const Blk rb = MASK == 7 ? (KD == 2 ? Blk{p, g, 0} : Blk{pn, gn, KD == 1 ? 2 : 1}) : rq;
+      auto wt = [&](const int i) __attribute__((always_inline)) { w_ticket(rb.g, rb.kd, rslot, i); };
+      auto at = [&](const int i) __attribute__((always_inline)) { act_ticket(nx, nslot, A0 + i, e[A0 + i]); };
+      block(apl, wl + slot * Cfg::WUNIT, s, within, [&](const int gi) __attribute__((always_inline)) {
+        if constexpr (NB == 1) tickets_act_first(gi, NW, NA, wt, at);
+        else tickets(gi, NW, NA, wt, at);
+      });
+      dma_wait_but<NB == 1 ? NW : NW + NA>();  // (the epilogue's stores are NOT counted: see the note on counted waits above)
+      mg_barrier();
+      if constexpr (MASK != 7) {
+        if constexpr (NW > 0) rq = blk_next(rq);
+        ring = __builtin_amdgcn_readfirstlane(ring == 2 ? 0 : ring + 1);
+      }
+    };
     auto nothing = [&](const int) __attribute__((always_inline)) {};
-    // kd = 2 (weight slot 0); requests: this unit's kd = 0 weights -> slot 2, first half of the next plane unit
-    block(do2, apl, wl + 0 * Cfg::WUNIT, s_m1, nothing, [&](const int gi) __attribute__((always_inline)) {
-      tickets(gi, NA0, [&](const int i) __attribute__((always_inline)) { w_ticket(r0, g, 0, 2, i); },
-              [&](const int i) __attribute__((always_inline)) { act_ticket(nx, nslot, i, e[i]); });
-    });
-    dma_wait_but<NWI + NA0>();
-    mg_barrier();
-    // kd = 1 (slot 1); requests: the next unit's kd = 2 weights -> slot 0, second half of the next plane unit.  In the plane's
-    // last group output plane p - 1 is complete: its rows are converted and stored under this block's MFMAs.
-    block(do1, apl, wl + 1 * Cfg::WUNIT, s_0,
-          [&](const int gi) __attribute__((always_inline)) { if constexpr (LAST) { if (gi < ROWS) epilogue_row(s_m1, do2 ? p - 1 : -1, gi); } },
-          [&](const int gi) __attribute__((always_inline)) {
-      tickets(gi, NA1, [&](const int i) __attribute__((always_inline)) { w_ticket(r2n, gn, 2, 0, i); },
-              [&](const int i) __attribute__((always_inline)) { act_ticket(nx, nslot, NA0 + i, e[NA0 + i]); });
-    });
-    dma_wait_but<NWI + NA1>();                 // (the epilogue's stores are NOT counted: see the note on counted waits above)
-    mg_barrier();
-    // kd = 0 (slot 2); requests: the next unit's kd = 1 weights -> slot 1
-    block(do0, apl, wl + 2 * Cfg::WUNIT, s_p1, nothing, [&](const int gi) __attribute__((always_inline)) {
-      tickets(gi, 0, [&](const int i) __attribute__((always_inline)) { w_ticket(r1n, gn, 1, 1, i); }, nothing);
-    });
-    dma_wait_but<NWI>();                       // ... which stay in flight; everything older (the whole next plane unit) has landed
-    mg_barrier();
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    if constexpr ((MASK & 4) != 0) live(I0{}, I2{}, s_m1, nothing);
+    if constexpr ((MASK & 2) != 0) {
+      // in the plane's last group output plane p - 1 is complete after kd = 2: its rows are converted and stored under this
+      // block's MFMAs
+      live(std::integral_constant<int, (MASK >> 2) & 1>{}, I1{}, s_0, [&](const int gi) __attribute__((always_inline)) {
+        if constexpr (LAST && (MASK & 4) != 0) { if (gi < ROWS) epilogue_row(s_m1, p - 1, gi); }
+      });
+    }
+    if constexpr ((MASK & 1) != 0) live(std::integral_constant<int, NB - 1>{}, I0{}, s_p1, nothing);
+    if constexpr (LAST && MASK == 4) {
+#pragma unroll
+      for (int row = 0; row < ROWS; ++row) epilogue_row(s_m1, p - 1, row);
+    }
     ++u;
   };
-  auto plane = [&](int p, f32x16 (&s_m1)[ROWS], f32x16 (&s_0)[ROWS], f32x16 (&s_p1)[ROWS]) __attribute__((always_inline)) {
-    for (int g = 0; g + 1 < ng; ++g) unit(std::false_type{}, p, g, s_m1, s_0, s_p1);
-    unit(std::true_type{}, p, ng - 1, s_m1, s_0, s_p1);
+  using NoTail = std::integral_constant<int, 0>;
+  auto plane = [&](auto mask_tag, int p, f32x16 (&s_m1)[ROWS], f32x16 (&s_0)[ROWS], f32x16 (&s_p1)[ROWS]) __attribute__((always_inline)) {
+    for (int g = 0; g + 1 < ng; ++g) unit(mask_tag, std::false_type{}, NoTail{}, p, g, s_m1, s_0, s_p1);
+    unit(mask_tag, std::true_type{}, NoTail{}, p, ng - 1, s_m1, s_0, s_p1);
+  };
+  using M001 = std::integral_constant<int, 1>;
+  using M010 = std::integral_constant<int, 2>;
+  using M011 = std::integral_constant<int, 3>;
+  using M100 = std::integral_constant<int, 4>;
+  using M110 = std::integral_constant<int, 6>;
+  using M111 = std::integral_constant<int, 7>;
+  // the segment's last plane d1 (mask 100, one block a unit): the last two units have no block after next (ng >= 2)
+  auto plane_out = [&](int p, f32x16 (&s_m1)[ROWS], f32x16 (&s_0)[ROWS], f32x16 (&s_p1)[ROWS]) __attribute__((always_inline)) {
+    for (int g = 0; g + 2 < ng; ++g) unit(M100{}, std::false_type{}, NoTail{}, p, g, s_m1, s_0, s_p1);
+    unit(M100{}, std::false_type{}, std::integral_constant<int, 1>{}, p, ng - 2, s_m1, s_0, s_p1);
+    unit(M100{}, std::true_type{}, std::integral_constant<int, 2>{}, p, ng - 1, s_m1, s_0, s_p1);
+  };
+  // planes d1 - 1 (mask 110) and d1 of a segment of two or more planes; behind 111 planes the ring and the cursor start over
+  auto lead_out = [&](int p, f32x16 (&s_m1)[ROWS], f32x16 (&s_0)[ROWS], f32x16 (&s_p1)[ROWS]) __attribute__((always_inline)) {
+    ring = 0;
+    rq = Blk{p, 1, 2};                                                 // (p, 0, 2) -> (p, 0, 1) -> (p, 1, 2)
+    plane(M110{}, p, s_m1, s_0, s_p1);
+    plane_out(p + 1, s_0, s_p1, s_m1);
   };
 
-  // prologue: first plane unit, the weights of its kd = 2 and kd = 1 blocks
+  // prologue: first plane unit, the weights of the first two live blocks (kd = 0 of groups 0 and 1 of plane d0 - 1)
   load_act(d0 - 1, 0, 0);
-  load_w(d0 - 1, 0, 2, 0);
-  load_w(d0 - 1, 0, 1, 1);
+  load_w(0, 0, 0);
+  load_w(1, 0, 1);
+  rq = blk_next(Blk{d0 - 1, 1, 0});
   dma_wait_all();
   __syncthreads();
   {
     f32x16 acc[3][ROWS];
     zero_set(acc[0]); zero_set(acc[1]); zero_set(acc[2]);
-    // input planes d0 - 1 .. d1 in triples (the rotation of the three register sets returns to its start after three planes,
-    // so the loop body needs no control flow between the planes -- with `if (p > d1) skip` joins inside the loop hipcc
-    // copied and spilled whole 64-register sets); the one or two planes left over run behind the loop, nested, where no
-    // accumulator is live across a join.
-    const int np = d1 - d0 + 2;
+    // Input planes d0 - 1 .. d1; output plane d0 + j lives in acc[(1 + j) % 3].  The masks are run-time per plane, the
+    // variants are not: a segment is lead-in (001, 011), 111 planes, lead-out (110, 100), with segments of one plane (001,
+    // 010, 100) and two planes (no 111 plane) as sequences of their own, chosen where every accumulator is still zero.
+    // The 111 planes run in triples (the rotation of the three register sets returns to its start after three planes, so
+    // the loop body needs no control flow between the planes -- with `if (p > d1) skip` joins inside the loop hipcc copied
+    // and spilled whole 64-register sets); the one or two left over and the lead-out run behind the loop, nested, where
+    // no accumulator is live across a join.
+    const int len = d1 - d0;
     int pb = d0 - 1;
-    for (int t3 = 0; t3 < np / 3; ++t3) {
-      plane(pb, acc[2], acc[0], acc[1]);
-      plane(pb + 1, acc[0], acc[1], acc[2]);
-      plane(pb + 2, acc[1], acc[2], acc[0]);
-      pb += 3;
-    }
-    if (np % 3 >= 1) {
-      plane(pb, acc[2], acc[0], acc[1]);
-      if (np % 3 == 2) plane(pb + 1, acc[0], acc[1], acc[2]);
+    if (len == 1) {
+      plane(M001{}, pb, acc[2], acc[0], acc[1]);
+      plane(M010{}, pb + 1, acc[0], acc[1], acc[2]);
+      plane_out(pb + 2, acc[1], acc[2], acc[0]);
+    } else {
+      plane(M001{}, pb, acc[2], acc[0], acc[1]);
+      plane(M011{}, pb + 1, acc[0], acc[1], acc[2]);
+      pb += 2;
+      if (len == 2) {
+        lead_out(pb, acc[1], acc[2], acc[0]);
+      } else {
+        // (the planes left over run IN FRONT of the triples, so that each remainder is one straight path -- left-over planes,
+        //  loop, lead-out -- with its own rotation; nested behind a common loop, the three lead-outs spilled)
+        const int n7 = len - 2, nt = n7 / 3;
+        auto triples = [&](f32x16 (&sa)[ROWS], f32x16 (&sb)[ROWS], f32x16 (&sc)[ROWS]) __attribute__((always_inline)) {
+          for (int t3 = 0; t3 < nt; ++t3) {
+            plane(M111{}, pb, sa, sb, sc);
+            plane(M111{}, pb + 1, sb, sc, sa);
+            plane(M111{}, pb + 2, sc, sa, sb);
+            pb += 3;
+          }
+        };
+        if (n7 % 3 == 0) {
+          triples(acc[1], acc[2], acc[0]);
+          lead_out(pb, acc[1], acc[2], acc[0]);
+        } else if (n7 % 3 == 1) {
+          plane(M111{}, pb, acc[1], acc[2], acc[0]);
+          pb += 1;
+          triples(acc[2], acc[0], acc[1]);
+          lead_out(pb, acc[2], acc[0], acc[1]);
+        } else {
+          plane(M111{}, pb, acc[1], acc[2], acc[0]);
+          plane(M111{}, pb + 1, acc[2], acc[0], acc[1]);
+          pb += 2;
+          triples(acc[0], acc[1], acc[2]);
+          lead_out(pb, acc[0], acc[1], acc[2]);
+        }
+      }
     }
   }
   dma_wait_all();
