@@ -667,6 +667,46 @@ int mi355_aug_motion(const float* x, float* out, int32_t c, int32_t d, int32_t h
 typedef struct mi355_scalar_table { const float* src[MI355_EPOCH_MAX_SCALARS]; } mi355_scalar_table;
 int mi355_epoch_accumulate(const mi355_scalar_table* table, int32_t n, double weight, double* acc, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MedicalNet ResNet-10 feature extractor, FORWARD ONLY -- the frozen network inside the reference's
+ * Perceptual term (src/model.py:123-138) and behind its FID metric (:158-163, 235-257).  Eval mode: every BatchNorm is folded
+ * into its convolution by the caller (w' = w g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps), in f32, before the
+ * weights are rounded to bf16).  Activations are DENSE bf16 NDHWC (ld == C), 16-byte aligned; bias is f32; f32 accumulation.
+ *   mi355_medicalnet_moments : mean_std[0] = mean, mean_std[1] = unbiased std of the n >= 2 floats of x, accumulated in f64;
+ *                              mean_std stays in DEVICE memory.  part: 2 * mi355_medicalnet_moments_blocks(n) doubles.
+ *   mi355_medicalnet_stem    : y = ReLU(Conv3d(1 -> 64, k7, s2, p3)(v) + bias) over `samples` contiguous f32 (d, h, w) volumes
+ *                              (every (batch, channel) pair of an NCDHW tensor is one sample), v = bf16((x - mean) / std) inside
+ *                              the volume and 0 in the padding; mean_std as written by mi355_medicalnet_moments ({0, 1}: none).
+ *                              wp: bf16 [25][64][16], element (s, co, e) = w[co][kd][kh][kw] with (kd, kh) = divmod(2s + e / 8, 7)
+ *                              and kw = e % 8; zero for kw == 7 and for the 50th pair.  Output extents (n - 1) / 2 + 1.
+ *   mi355_medicalnet_maxpool : MaxPool3d(k3, s2, p1) of a (samples, d, h, w, c) tensor, c % 8 == 0; padding counts as -inf.
+ *   mi355_medicalnet_conv    : y = act(conv(x) + bias [+ residual]), act = ReLU if relu != 0.  ks 3 with stride 1 or 2,
+ *                              dilation 1, 2 or 4 and padding = dilation, or ks 1 (the downsample) with stride 1 or 2;
+ *                              cin and cout in {64, 128, 256, 512}; anything else returns MI355_ERR_UNSUPPORTED.
+ *                              wp: bf16 [ks^3][cin / 16][cout][16], element (tap, q, co, e) = w[co][16 q + e][kd][kh][kw].
+ *                              residual (may be NULL) has the shape of y.  Output extents (n - 1) / stride + 1.
+ *   mi355_medicalnet_tail    : feat_*: (items * c, vox, 512) bf16, the layer4 outputs of the c channel volumes of each item; a
+ *                              voxel's feature vector f is the c * 512 channels of its item.  Writes
+ *                                mean_*[item][c * 512]  spatial means (the FID features),
+ *                                item_sum[item] = sum over voxels of sum_ch (fp / (|fp| + 1e-10) - ft / (|ft| + 1e-10))^2,
+ *                                value[0]       = sum of item_sum / (items * vox)   (the Perceptual distance).
+ *                              workspace: mi355_medicalnet_tail_workspace_bytes(items, c, vox) bytes, 16-byte aligned.
+ * Extents: any d, h, w >= 1 with fewer than 2^31 voxels per sample.  No atomics: every reduction runs in a fixed order, calls
+ * are bit-identical.  No host synchronisation and no host read, so the calls record into a hipGraph.
+ * ---------------------------------------------------------------------------------------- */
+int32_t mi355_medicalnet_moments_blocks(int64_t n);
+int mi355_medicalnet_moments(const float* x, int64_t n, double* part, float* mean_std, void* stream);
+int mi355_medicalnet_stem(const float* x, const float* mean_std, const void* wp, const float* bias, void* y, int32_t samples,
+                          int32_t d, int32_t h, int32_t w, void* stream);
+int mi355_medicalnet_maxpool(const void* x, void* y, int32_t samples, int32_t d, int32_t h, int32_t w, int32_t c, void* stream);
+int mi355_medicalnet_conv(const void* x, const void* wp, const float* bias, const void* residual, void* y, int32_t samples,
+                          int32_t d, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t ks, int32_t stride,
+                          int32_t dilation, int32_t relu, void* stream);
+int64_t mi355_medicalnet_tail_workspace_bytes(int32_t items, int32_t c, int32_t vox);
+int mi355_medicalnet_tail(const void* feat_pred, const void* feat_target, int32_t items, int32_t c, int32_t vox,
+                          void* workspace, int64_t workspace_bytes, float* mean_pred, float* mean_target, float* item_sum,
+                          float* value, void* stream);
+
 /* layout probe used by the tests: writes lane -> (row, col) maps of the MFMA accumulators */
 int mi355_mfma_selftest(float* out_f32_1024, float* out_bf16_1024, void* stream);
 

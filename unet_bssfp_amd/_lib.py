@@ -172,6 +172,13 @@ _SIGNATURES = {
     "mi355_rigid_resample": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp]),
     "mi355_aug_motion": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mi355_epoch_accumulate": (C.c_int, [C.POINTER(ScalarTable), _i32, C.c_double, _vp, _vp]),
+    "mi355_medicalnet_moments_blocks": (_i32, [_i64]),
+    "mi355_medicalnet_moments": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "mi355_medicalnet_stem": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mi355_medicalnet_maxpool": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mi355_medicalnet_conv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mi355_medicalnet_tail_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "mi355_medicalnet_tail": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "mi355_mfma_selftest": (C.c_int, [_vp, _vp, _vp]),
     "mi355_amax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "mi355_amax_act": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _vp, _vp]),

@@ -6,7 +6,9 @@ The reference trains under ``pl.Trainer`` with ``ModelCheckpoint`` (src/train.py
 
     'state_dict'        module state, keys prefixed by the LightningModule attribute: ``gen.*`` / ``discr.*``
                         (key table: SURVEY.md 8(b)); a reference checkpoint also carries
-                        ``recon_criterion.*`` (MedicalNet weights of the Perceptual term) -- ignored here
+                        ``recon_criterion.*`` (MedicalNet weights of the Perceptual term) -- not loaded into the
+                        model (listed under 'ignored_keys'); ``medicalnet_state_dict`` extracts them for
+                        ``medicalnet.MedicalNetResNet10``
     'optimizer_states'  [gen AdamW state_dict, discr AdamW state_dict]   (configure_optimizers order, :359-361)
     'hyper_parameters'  what ``save_hyperparameters`` recorded (src/model.py:149): input_modality, lr,
                         batch_size, perceptual_factor, recon_factor
@@ -95,6 +97,24 @@ def apply_checkpoint(model, ckpt: Dict, strict: bool = True, load_optimizers: bo
         from .functional import DropoutState
         DropoutState.base(next(model.gen.parameters()).device).fill_(int(base))
     return {"epoch": ckpt.get("epoch", 0), "global_step": ckpt.get("global_step", 0), "ignored_keys": ignored}
+
+
+def medicalnet_state_dict(ckpt_or_path) -> Dict[str, torch.Tensor]:
+    """The MedicalNet ResNet-10 weights a reference checkpoint carries under ``recon_criterion.<...>.``, without the prefix:
+    ``MedicalNetResNet10().load_state_dict(medicalnet_state_dict(path))``.  The prefix is found by the stem's key: the one
+    that ends in ``conv1.weight`` and has the shape (64, 1, 7, 7, 7).  ``KeyError`` if the checkpoint has no such network."""
+    ckpt = ckpt_or_path
+    if not isinstance(ckpt, dict):
+        ckpt = torch.load(ckpt_or_path, map_location="cpu", weights_only=True)
+    sd = ckpt.get("state_dict", ckpt)
+    tail = "conv1.weight"
+    stems = [k for k, v in sd.items() if k.startswith("recon_criterion.") and k.endswith(tail)
+             and isinstance(v, torch.Tensor) and tuple(v.shape) == (64, 1, 7, 7, 7)]
+    if not stems:
+        raise KeyError("no MedicalNet ResNet-10 in the checkpoint: no key under 'recon_criterion.' ends in 'conv1.weight' "
+                       "with shape (64, 1, 7, 7, 7)")
+    prefix = stems[0][:-len(tail)]
+    return {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
 
 
 def load_from_checkpoint(path: str, device: Optional[str] = None, **overrides):

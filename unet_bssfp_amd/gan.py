@@ -11,10 +11,12 @@
   by the caller (no host sync inside the step)
 * DDP gradient all-reduce                         -> ``GradSync`` hooks (``ddp.py``), one per network
 
-The Perceptual term (src/model.py:127-129) needs remotely fetched MedicalNet weights; it is a
-pluggable slot (``extra_recon_terms``) and absent by default, as stated wherever numbers are
-reported.  The module is agnostic of where ``gen``/``discr`` come from, so the same step logic
-drives the CPU oracle modules in the tests.
+The Perceptual term (src/model.py:127-129) runs on the MedicalNet ResNet-10 (``medicalnet.py``).  Its
+forward is built, its backward is absent: with ``medicalnet=net`` the model logs the Perceptual distance
+and FID as validation / test metrics, and the training objective is unchanged -- the term stays out of
+the pluggable slot (``extra_recon_terms``), as stated wherever numbers are reported.  The module is
+agnostic of where ``gen``/``discr`` come from, so the same step logic drives the CPU oracle modules in
+the tests.
 """
 from __future__ import annotations
 
@@ -42,7 +44,7 @@ class bSSFPToDWITensorModel(nn.Module):
                  gen: Optional[nn.Module] = None, discr: Optional[nn.Module] = None,
                  l1_fn: Optional[Callable] = None, optimizer_class=None,
                  extra_recon_terms: Optional[Dict[str, Callable]] = None, recon_divisor: Optional[int] = None,
-                 reference_quirks: bool = False):
+                 reference_quirks: bool = False, medicalnet: Optional[nn.Module] = None):
         super().__init__()
         self.input_modality = input_modality
         if gen is None or discr is None:
@@ -62,6 +64,10 @@ class bSSFPToDWITensorModel(nn.Module):
         # True: test_step feeds compute_metrics what the reference feeds it (src/model.py:303-307: the aggregated INPUT
         # volume under the name pred_tensor) instead of the aggregated prediction
         self.reference_quirks = reference_quirks
+        # a medicalnet.MedicalNetResNet10 on the device: compute_metrics also logs {step}_metric_FID and
+        # {step}_metric_Perceptual (value * perceptual_factor).  Held outside the module tree: it is frozen, it is not the
+        # model's to save (state_dict, checkpoints and optimizers see gen and discr only) and it does not enter the objective.
+        self._medicalnet = (medicalnet,)
         self.grad_sync_gen = None      # set by ddp.attach(); called after each phase's backward
         self.grad_sync_discr = None
         self.sinks_gen = None          # gradsink.GradBuckets of the HIP networks (created at the first training step)
@@ -371,13 +377,21 @@ class bSSFPToDWITensorModel(nn.Module):
     def compute_metrics(self, y_hat, y, step_name, logs=None):
         """``self.log(f'{step_name}_metric_{name}', metric_fn(y_hat, y).mean())`` for every entry of
         ``metric_fns`` (src/model.py:215-220).  Default list: PSNR(1), SSIM(3-D, data_range 1), L1 on the
-        device (``metrics.reference_metric_fns``); the reference's FID entry needs remote weights."""
+        device (``metrics.reference_metric_fns``).  With ``medicalnet`` given, one run of the extractor per tensor also
+        yields the reference's FID entry and the Perceptual distance times ``perceptual_factor`` (a metric here: its
+        backward is not built, so it is no term of the objective)."""
         if getattr(self, "metric_fns", None) is None:
             from .metrics import reference_metric_fns
             self.metric_fns = reference_metric_fns()
         logs = self.last_logs if logs is None else logs
         for metric_fn, name in self.metric_fns:
             logs[f"{step_name}_metric_{name}"] = metric_fn(y_hat, y).mean()
+        if self._medicalnet[0] is not None:
+            from .medicalnet import medicalnet_distances
+            from .metrics import fid_from_features
+            value, feat_hat, feat_y = medicalnet_distances(self._medicalnet[0], y_hat.detach(), y.detach())
+            logs[f"{step_name}_metric_FID"] = fid_from_features(feat_hat, feat_y).float()
+            logs[f"{step_name}_metric_Perceptual"] = value.reshape(()) * self.perceptual_factor
         return logs
 
     @torch.no_grad()

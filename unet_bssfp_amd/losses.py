@@ -3,8 +3,12 @@
 The reference's objective sums L1, 1 - SSIM and the MedicalNet Perceptual term (thesis, 03-methods; src/model.py:209
 averages the terms of the slot).  ``SSIMLoss`` has the constructor signature of ``monai.losses.SSIMLoss``; MONAI is
 absent from this image, so parity with it is UNPINNED, as for ``metrics.SSIMMetric``: the formulas are the ones restated
-in oracle/metrics_ref.py, and the tests check value and gradient against that oracle in f64.  The Perceptual term needs
-remotely fetched weights and is not provided.
+in oracle/metrics_ref.py, and the tests check value and gradient against that oracle in f64.
+
+``PerceptualLoss`` is the VALUE of the MedicalNet Perceptual term on the frozen ResNet-10 of ``medicalnet.py`` (weights:
+``checkpoint.medicalnet_state_dict``; parity with MONAI's ``PerceptualLoss(network_type="medicalnet_resnet10_23datasets")``
+unpinned for the same reason).  Its forward is built, its backward is ABSENT: it serves as a validation / test quantity and
+refuses tensors that require grad, so it cannot sit in ``extra_recon_terms`` of a training step yet.
 
     model = bSSFPToDWITensorModel("bssfp", extra_recon_terms={"SSIM": SSIMLoss(3)})   # recon = (L1 + SSIM) / 2 * recon_factor
 """
@@ -15,6 +19,7 @@ from torch import nn
 
 from . import _lib
 from .functional import SSIM3dFn
+from .medicalnet import MedicalNetResNet10, medicalnet_distances
 
 
 class SSIMLoss(nn.Module):
@@ -59,3 +64,34 @@ class SSIMLoss(nn.Module):
         if self.reduction == "sum":
             return loss.sum()
         return loss
+
+
+class PerceptualLoss(nn.Module):
+    """The reference's Perceptual distance (MONAI ``MedicalNetPerceptualSimilarity``, ``channel_wise=False``), forward only.
+
+    Prediction and target are each normalised over the whole tensor, every channel runs through the ResNet-10 as its own
+    volume, the C outputs are concatenated to (B, 512 C, d, h, w), and with f^ = f / (sqrt(sum_ch f^2) + 1e-10) the value is
+    the mean over batch and positions of sum_ch (f^_input - f^_target)^2.  The model multiplies it by ``perceptual_factor``.
+    The whole forward stays on the device (no host read), so it records into a hipGraph.  There is no backward: an
+    ``input`` or ``target`` that requires grad raises ``NotImplementedError``."""
+
+    def __init__(self, net: MedicalNetResNet10, spatial_dims: int = 3):
+        super().__init__()
+        if spatial_dims != 3:
+            raise NotImplementedError("only the reference's 3-D configuration is built")
+        self._net = (net,)                                            # not a submodule: the frozen network is shared, not owned
+
+    @property
+    def net(self) -> MedicalNetResNet10:
+        return self._net[0]
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if input.requires_grad or target.requires_grad:
+            raise NotImplementedError("PerceptualLoss: only the forward is built; the backward pass through the MedicalNet "
+                                      "ResNet-10 is missing, so the term cannot be trained on -- detach both tensors")
+        if not (input.is_cuda and target.is_cuda):
+            raise _lib.Mi355Error("PerceptualLoss runs on the GPU only (no CPU fallback)")
+        if input.dim() != 5:
+            raise ValueError(f"input should have 5 dimensions (batch, channel, D, H, W), got {input.dim()}.")
+        value, _, _ = medicalnet_distances(self.net, input, target)
+        return value.reshape(())

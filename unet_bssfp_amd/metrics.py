@@ -4,7 +4,9 @@ Callables with the constructor signatures and (B, 1) results of the MONAI metric
 instantiates at src/model.py:158-160 -- ``PSNRMetric(max_val)``, ``SSIMMetric(spatial_dims, data_range)``,
 ``MAEMetric()`` -- so that ``compute_metrics`` (:215-220) stays as it is: ``metric_fn(y_hat, y).mean()``.
 MONAI is absent from this image; formulas restated in oracle/metrics_ref.py (parity unpinned).
-The FID entry of the reference's list needs the remotely fetched MedicalNet weights and is not provided.
+The FID entry of the reference's list (``compute_fid_medicalnet``, src/model.py:235-257) is ``FIDMedicalNet`` on the
+ResNet-10 of ``medicalnet.py``; it joins the list only when a network is given (the weights come out of a reference
+checkpoint: ``checkpoint.medicalnet_state_dict``).
 """
 from __future__ import annotations
 
@@ -89,6 +91,42 @@ class SSIMMetric:
         return out.float()
 
 
-def reference_metric_fns():
-    """the list of src/model.py:158-160 without the FID entry"""
-    return [[PSNRMetric(1), "PSNR"], [SSIMMetric(3, data_range=1), "SSIM"], [MAEMetric(), "L1"]]
+def fid_from_features(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Frechet distance of two feature sets (B, p) in f64: |mu_x - mu_y|^2 + tr Sx + tr Sy - 2 tr sqrt(Sx Sy), sample
+    covariances (divisor B - 1).  The p x p matrices are never formed: with the centred A = (x - mu_x) / sqrt(B - 1) and
+    B likewise, tr Sx = |A|_F^2, tr Sy = |B|_F^2 and tr sqrt(Sx Sy) is the sum of the singular values of the B x B matrix
+    A B^T.  Runs where the features live; NaN for fewer than two items (the covariance is undefined)."""
+    x, y = x.double(), y.double()
+    if x.shape[0] < 2 or y.shape[0] < 2:
+        return torch.full((), float("nan"), dtype=torch.float64, device=x.device)
+    mx, my = x.mean(0), y.mean(0)
+    a = (x - mx) / math.sqrt(x.shape[0] - 1)
+    b = (y - my) / math.sqrt(y.shape[0] - 1)
+    sv = torch.linalg.svdvals(a @ b.T)
+    return (mx - my).pow(2).sum() + a.pow(2).sum() + b.pow(2).sum() - 2 * sv.sum()
+
+
+class FIDMedicalNet:
+    """``compute_fid_medicalnet(y_hat, y)`` of the reference: features are the spatial means of the concatenated ResNet-10
+    outputs, (B, 512 C).  The extractor and the means run in HIP without a host read; the last step is a B x B SVD in f64
+    through ``torch.linalg.svdvals`` on the device, whose backend may synchronise with the host -- the one place where this
+    forward may wait (and why FID is left out of hipGraph captures).  Returns a 0-dim f32 tensor."""
+
+    def __init__(self, net):
+        self.net = net
+
+    def __call__(self, y_pred, y):
+        from .medicalnet import medicalnet_distances
+        a, b = _prep(y_pred, y)
+        if a.dim() != 5:
+            raise ValueError(f"y_pred should have 5 dimensions (batch, channel, D, H, W), got {a.dim()}.")
+        _, fp, ft = medicalnet_distances(self.net, a, b)
+        return fid_from_features(fp, ft).float()
+
+
+def reference_metric_fns(medicalnet=None):
+    """the list of src/model.py:158-163; the FID entry is appended only when a ``MedicalNetResNet10`` is given"""
+    fns = [[PSNRMetric(1), "PSNR"], [SSIMMetric(3, data_range=1), "SSIM"], [MAEMetric(), "L1"]]
+    if medicalnet is not None:
+        fns.append([FIDMedicalNet(medicalnet), "FID"])
+    return fns

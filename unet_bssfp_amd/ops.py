@@ -982,3 +982,90 @@ def mfma_selftest(device) -> Tuple[torch.Tensor, torch.Tensor]:
     b = torch.zeros(1024, dtype=torch.float32, device=device)
     _lib.check(_lib.load().mi355_mfma_selftest(a.data_ptr(), b.data_ptr(), _stream()), "mfma_selftest")
     return a.view(32, 32), b.view(32, 32)
+
+
+# ---------------------------------------------------------------------------------------------- MedicalNet ResNet-10 (forward only)
+def _out_extent(n: int, stride: int) -> int:
+    return (n - 1) // stride + 1
+
+
+def _bf16_act(t: torch.Tensor, what: str):
+    require_cuda(t)
+    if t.dtype != torch.bfloat16 or t.dim() != 5 or not t.is_contiguous():
+        raise ValueError(f"{what}: need a contiguous bfloat16 (N, D, H, W, C) tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def medicalnet_moments(x: torch.Tensor) -> torch.Tensor:
+    """-> f32[2] on the device: (mean, unbiased std) over the whole tensor, accumulated in f64.  No host read."""
+    require_cuda(x)
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    lib = _lib.load()
+    part = torch.empty(2 * lib.mi355_medicalnet_moments_blocks(x.numel()), dtype=torch.float64, device=x.device)
+    out = torch.empty(2, dtype=torch.float32, device=x.device)
+    _lib.check(lib.mi355_medicalnet_moments(x.data_ptr(), x.numel(), part.data_ptr(), out.data_ptr(), _stream()),
+               "medicalnet_moments")
+    return out
+
+
+def medicalnet_stem(x: torch.Tensor, mean_std: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """x: contiguous f32 (S, D, H, W) volumes -> bf16 (S, D', H', W', 64) = ReLU(conv1(bf16((x - mean) / std)) + bias)"""
+    require_cuda(x, mean_std, wp, bias)
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+    assert mean_std.dtype == torch.float32 and mean_std.numel() == 2
+    assert wp.dtype == torch.bfloat16 and wp.numel() == 25 * 64 * 16 and wp.is_contiguous()
+    assert bias.dtype == torch.float32 and bias.numel() == 64
+    s, d, h, w = x.shape
+    y = torch.empty((s, _out_extent(d, 2), _out_extent(h, 2), _out_extent(w, 2), 64), dtype=torch.bfloat16, device=x.device)
+    _lib.check(_lib.load().mi355_medicalnet_stem(x.data_ptr(), mean_std.data_ptr(), wp.data_ptr(), bias.data_ptr(), y.data_ptr(),
+                                                 s, d, h, w, _stream()), "medicalnet_stem")
+    return y
+
+
+def medicalnet_maxpool(x: torch.Tensor) -> torch.Tensor:
+    """MaxPool3d(k3, s2, p1) of a bf16 (S, D, H, W, C) tensor"""
+    _bf16_act(x, "medicalnet_maxpool")
+    s, d, h, w, c = x.shape
+    y = torch.empty((s, _out_extent(d, 2), _out_extent(h, 2), _out_extent(w, 2), c), dtype=torch.bfloat16, device=x.device)
+    _lib.check(_lib.load().mi355_medicalnet_maxpool(x.data_ptr(), y.data_ptr(), s, d, h, w, c, _stream()), "medicalnet_maxpool")
+    return y
+
+
+def medicalnet_conv(x: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, cout: int, ks: int = 3, stride: int = 1,
+                    dilation: int = 1, residual: Optional[torch.Tensor] = None, relu: bool = True) -> torch.Tensor:
+    """bf16 (S, D, H, W, Cin) -> bf16 (S, D', H', W', cout): act(conv(x) + bias [+ residual]); padding = dilation * (ks // 2).
+    wp: bf16 [ks^3][Cin / 16][cout][16] (medicalnet.pack_conv_weight)."""
+    _bf16_act(x, "medicalnet_conv")
+    require_cuda(wp, bias, residual)
+    s, d, h, w, cin = x.shape
+    assert wp.dtype == torch.bfloat16 and wp.is_contiguous() and wp.numel() == ks ** 3 * cin * cout
+    assert bias.dtype == torch.float32 and bias.numel() == cout
+    y = torch.empty((s, _out_extent(d, stride), _out_extent(h, stride), _out_extent(w, stride), cout), dtype=torch.bfloat16,
+                    device=x.device)
+    if residual is not None:
+        _bf16_act(residual, "medicalnet_conv residual")
+        assert residual.shape == y.shape
+    _lib.check(_lib.load().mi355_medicalnet_conv(x.data_ptr(), wp.data_ptr(), bias.data_ptr(), _ptr(residual), y.data_ptr(),
+                                                 s, d, h, w, cin, cout, ks, stride, dilation, int(relu), _stream()),
+               "medicalnet_conv")
+    return y
+
+
+def medicalnet_tail(feat_pred: torch.Tensor, feat_target: torch.Tensor, items: int, channels: int):
+    """feat_*: bf16 (items * channels, d, h, w, 512) -> (value f32[1], item_sum f32[items], mean_pred, mean_target
+    f32 (items, channels * 512)): the Perceptual distance and the FID features in one pass."""
+    _bf16_act(feat_pred, "medicalnet_tail")
+    _bf16_act(feat_target, "medicalnet_tail")
+    assert feat_pred.shape == feat_target.shape and feat_pred.shape[0] == items * channels and feat_pred.shape[4] == 512
+    vox = feat_pred.shape[1] * feat_pred.shape[2] * feat_pred.shape[3]
+    lib = _lib.load()
+    need = lib.mi355_medicalnet_tail_workspace_bytes(items, channels, vox)
+    dev = feat_pred.device
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    mp = torch.empty((items, channels * 512), dtype=torch.float32, device=dev)
+    mt = torch.empty_like(mp)
+    item_sum = torch.empty(items, dtype=torch.float32, device=dev)
+    value = torch.empty(1, dtype=torch.float32, device=dev)
+    _lib.check(lib.mi355_medicalnet_tail(feat_pred.data_ptr(), feat_target.data_ptr(), items, channels, vox, work.data_ptr(), need,
+                                         mp.data_ptr(), mt.data_ptr(), item_sum.data_ptr(), value.data_ptr(), _stream()),
+               "medicalnet_tail")
+    return value, item_sum, mp, mt
