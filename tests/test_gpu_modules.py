@@ -90,12 +90,10 @@ def test_discriminator_golden(hip, golden_dir, tag, modality, n, s, cin):
     d = d.to(DEV).train()
     x, y = R.synthetic_batch(n, s, seed=1234, cin=cin)
     xd, yd = x.to(DEV), y.to(DEV).requires_grad_(True)
-    from unet_bssfp_amd import functional as Fn
-    Fn.S2D_POISON = True                  # space-to-depth tensors start as NaN: every slot must be written by the kernels
-    try:
+    from tests.alloc_poison import poisoned
+    with poisoned("nan") as poison:       # EVERY allocation of the call starts as NaN: each slot that is read must have been written
         logits = d(xd, yd)
-    finally:
-        Fn.S2D_POISON = False
+    assert poison.filled >= 1
     assert bool(torch.isfinite(logits).all())
     loss = F.binary_cross_entropy_with_logits(logits, torch.ones_like(logits))
     loss.backward()

@@ -107,14 +107,10 @@ def _padded(vec: Optional[torch.Tensor], n: int, fill: float = 0.0) -> Optional[
 
 
 # ====================================================================================== backward stages
-S2D_POISON = False      # tests: fill new space-to-depth tensors with NaN to prove that the kernels write every slot
-
-
 def _new_s2d(shape, dtype, device):
     """A space-to-depth output tensor.  Not zero-filled: the pack / norm+act kernels write every (cell, block) slot, the
-    out-of-volume blocks of the border cells included (elementwise_common.h: s2d_zero_siblings)."""
-    if S2D_POISON:
-        return torch.full(shape, float("nan"), dtype=dtype, device=device)
+    out-of-volume blocks of the border cells included (elementwise_common.h: s2d_zero_siblings); tests/alloc_poison.py
+    fills it, like every other allocation, with NaN and with a huge value to prove that."""
     return torch.empty(shape, dtype=dtype, device=device)
 
 
