@@ -53,8 +53,11 @@ def _scalar(ptr):
 
 def _family(pid):
     """Kernel family from the plan id (10000 ks + 1000 halo + 100 shape + 10 vt + ct)."""
-    s = (pid % 10000) // 100
-    return {20: "march", 21: "marchg", 22: "lowg", 23: "lowg", 24: "march2", 19: "ru"}.get(s, f"k{pid // 10000} shape {s % 10}")
+    from unet_bssfp_amd import ops
+    p = ops.decode_plan_id(pid)
+    names = {ops.SHAPE_MARCH: "march", ops.SHAPE_MARCHG: "marchg", ops.SHAPE_LOWG_W16: "lowg", ops.SHAPE_LOWG_W8: "lowg",
+             ops.SHAPE_MARCH2: "march2", ops.SHAPE_RU: "ru"}
+    return names.get(p.shape, f"k{p.ks} shape {p.shape}") if p.halo else f"k{p.ks} shape {p.shape}"
 
 
 def _pair(a):

@@ -614,7 +614,7 @@ def test_discriminator_first_block_split_equals_the_unsplit_network(hip):
         n_add = sum(1 for _, a in launches if a)
         assert n_add == (2 if split else 0), launches              # one y-part launch per use; the x-part ran once (memo)
         if split:
-            assert sum(1 for pid, a in launches if (pid % 10000) // 100 == 24 and not a) >= 1
+            assert sum(1 for pid, a in launches if ops.decode_plan_id(pid)[1:3] == (1, ops.SHAPE_MARCH2) and not a) >= 1
         res[split] = (la.detach().float().cpu(), yg.grad.cpu(), both.detach().float().cpu(),
                       {n: p.grad.detach().cpu() for n, p in d.named_parameters() if p.grad is not None})
     a, b = res[True], res[False]

@@ -689,7 +689,7 @@ def test_split_s2d_conv_equals_the_conv_of_the_concatenation(hip, ny, summed):
         _ops().CONV_PROBE = None
     # x-part once (f32 out), y-part twice with the addend; all on the marching k2 kernel
     assert [p[1:] for p in plans] == [(False, 1, 0), (True, 0, 1 if ny > 1 else 0), (True, 0, 1 if ny > 1 else 0)], plans
-    assert all((p[0] % 10000) // 100 == 24 for p in plans), plans
+    assert all(_ops().decode_plan_id(p[0])[1:3] == (1, _ops().SHAPE_MARCH2) for p in plans), plans
     assert torch.equal(z, z2)
     close(from_act(z, cout), z_ref.detach(), dtype, "z")
     zc = z_ref.detach() - b_cpu.detach().view(1, -1, 1, 1, 1)
@@ -945,7 +945,7 @@ def test_upcat_fused_up_branch_matches_torch(hip, n, ce, cl, cu, co, low):
         z.backward(to_act(gz, dtype))
     finally:
         _ops().CONV_PROBE = None
-    assert sum(1 for p in plans if p[1]) == 1 and all((p[0] % 10000) // 100 == 24 for p in plans if p[1]), plans
+    assert sum(1 for p in plans if p[1]) == 1 and all(_ops().decode_plan_id(p[0])[1:3] == (1, _ops().SHAPE_MARCH2) for p in plans if p[1]), plans
     close(from_act(a_e.grad, ce), x_e.grad, dtype, "dx_e")
     z_q.backward(gz)
     close(from_act(a_l.grad, cl), xl2.grad, dtype, "dx_low (bf16 k4)")

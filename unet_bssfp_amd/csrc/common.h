@@ -197,3 +197,27 @@ __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0
 __device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// ---- host planner helpers (conv_api.hip, wgrad.hip) ----
+// A planner constant: constexpr in the shipped build; in the diagnostic build (-DMI355_DIAG, tools/build_diag.sh into
+// tools/_build/, never shipped) read once from the environment variable ENV, default the shipped value (tools/sweep_plan.sh).
+#ifdef MI355_DIAG
+#include <stdlib.h>
+#define MI355_PLANNER_CONSTANT(fn, ENV, shipped) \
+  static int fn() { static const int v = [] { const char* e = getenv(ENV); return e ? atoi(e) : (shipped); }(); return v; }
+#else
+#define MI355_PLANNER_CONSTANT(fn, ENV, shipped) constexpr int fn() { return (shipped); }
+#endif
+
+// A kernel that declares more than 64 KB of dynamic LDS needs its limit raised once per process (here: once per kernel, at its
+// first launch); MI355_OK on success.  A failure (another driver or LDS carve-out) is reported by the kernel's name at the
+// launch site instead of as a generic launch error later.
+template <auto Kernel>
+static int raise_lds_limit(const char* name, int bytes) {
+  static const int err = (int)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (err) {
+    mi355_set_error("%s: cannot raise the dynamic LDS limit to %d bytes (hip error %d)", name, bytes, err);
+    return MI355_ERR_HIP;
+  }
+  return MI355_OK;
+}

@@ -1092,18 +1092,44 @@ __global__ __launch_bounds__(256, 1) void wgrad_pw_kernel(const WgradArgs a, con
   }
 }
 
+// which kernel writes the slabs: the values mi355_conv_wgrad_plan_kind returns
+enum WKind : int {
+  kWGeneric = 0,   // wgrad_kernel: any dtype / ks / stride / g grid
+  kWTile = 1,      // wgrad_bf16_kernel (deconv4: wgrad_deconv_kernel): bf16, stride 1, g on the grid of the outputs
+  kWMarch = 2,     // wgrad_march_kernel: 3x3x3, padding 1, same extents, wide rows
+  kWPointwise = 3, // wgrad_pw_kernel: streaming 1x1x1, one (ci, co) tile
+  kWMarch2 = 4,    // wgrad_march2_kernel: dense 2x2x2, padding 0, wide rows
+};
+
 struct WPlan { int ks, tpw, tap_groups, ci_tiles, co_tiles, splits, cinp32, coutp32; long long rows;
-               bool fast, deconv4; int shape, tiles_d, tiles_h, tiles_w, ntiles, nslabs;
-               bool march; int seg_len, nseg; bool pw; bool march2; };
+               int kind; bool deconv4; int shape, tiles_d, tiles_h, tiles_w, ntiles, nslabs;
+               int seg_len, nseg; };
 
 const int kWTD[2] = {2, 2}, kWTH[2] = {4, 8}, kWTW[2] = {32, 16};
 
 // planner constant of the tile path as a diagnostic-build knob (tools/sweep_plan.sh)
-#ifdef MI355_DIAG
-int tune_wg_target() { static const int v = [] { const char* e = getenv("MI355_WG_TARGET"); return e ? atoi(e) : 512; }(); return v; }
-#else
-constexpr int tune_wg_target() { return 512; }
-#endif
+MI355_PLANNER_CONSTANT(tune_wg_target, "MI355_WG_TARGET", 512)
+
+constexpr long long kSlabCap = 256ll << 20;        // the slab workspace stays below ~256 MiB
+
+// d-segments of the two marching kernels (th x tw footprints per sample): the depth is cut into 1 .. depth / min_len segments of
+// ceil(depth / ns) planes (cuts whose last segment would be empty are skipped); whole rounds of 256 workgroups (one per CU),
+// cost = rounds x (planes per segment + pipeline fill); one slab per footprint and segment, under the workspace cap.
+void set_wgrad_segments(const mi355_wgrad_desc* d, WPlan* p, int th, int tw, int min_len, long long slab_bytes) {
+  const long long fp = (long long)d->n * th * tw, base = fp * p->ci_tiles * p->co_tiles;
+  long long best = -1; int best_ns = 1;
+  for (int ns = 1; ns <= d->do_ / min_len; ++ns) {
+    const int L = ceil_div(d->do_, ns);
+    if ((long long)(ns - 1) * L >= d->do_) continue;
+    const long long wgs = base * ns, cost = ((wgs + 255) / 256) * (L + 3);
+    if (ns * fp * slab_bytes > kSlabCap) break;
+    if (best < 0 || cost < best) { best = cost; best_ns = ns; }
+  }
+  p->nseg = best_ns;
+  p->seg_len = ceil_div(d->do_, best_ns);
+  p->tiles_h = th; p->tiles_w = tw;
+  p->nslabs = d->n * th * tw * best_ns;
+}
 
 int wplan(const mi355_wgrad_desc* d, WPlan* p) {
   MI355_REQUIRE(d && d->x0 && d->g && d->dw, "wgrad: null pointer");
@@ -1115,6 +1141,7 @@ int wplan(const mi355_wgrad_desc* d, WPlan* p) {
   MI355_REQUIRE(d->s2d_cp == 0 || (d->s2d_cp % 8 == 0 && d->c1 == 0 && d->c0 == 8 * d->s2d_cp && d->cin <= d->s2d_cp),
                 "wgrad: bad space-to-depth operand");
   MI355_REQUIRE(d->xn >= 0 && (d->xn == 0 || d->n % d->xn == 0), "wgrad: xn must divide n");
+  *p = WPlan{};                 // kind kWGeneric
   p->ks = d->ks;
   p->tpw = d->ks == 1 ? 1 : (d->ks == 3 ? 9 : 8);
   const int nt = d->ks * d->ks * d->ks;
@@ -1129,91 +1156,56 @@ int wplan(const mi355_wgrad_desc* d, WPlan* p) {
   if (s < 1) s = 1;
   const long long max_s = (p->rows + 3) / 4;
   if (s > max_s) s = max_s;
-  // cap the slab workspace at ~256 MiB
   const long long slab_bytes = (long long)nt * p->cinp32 * p->coutp32 * 4;
-  while (s > 1 && s * 4 * slab_bytes > (256ll << 20)) s /= 2;
+  while (s > 1 && s * 4 * slab_bytes > kSlabCap) s /= 2;
   p->splits = (int)s;
   p->nslabs = p->splits * 4;
-  // fast path: bf16, 3x3x3 stride 1, g on the same grid as the outputs
+  // tile path: bf16, stride 1, g on the same grid as the outputs
   const bool cls = d->g_cls_cout > 0;
   MI355_REQUIRE(!cls || (d->dtype == MI355_DT_BF16 && d->ks == 1 && d->stride == 1 && d->g_cls_cout % 32 == 0 &&
                          d->cg >= d->g_cls_cout && d->gd == 2 * d->do_ && d->gh == 2 * d->ho && d->gw == 2 * d->wo &&
                          d->c1 == 0 && d->cout <= d->g_cls_cout),
                 "wgrad: bad transposed-conv class folding");
-  p->fast = d->dtype == MI355_DT_BF16 && d->stride == 1 && d->ld0 % 8 == 0 && (d->c1 == 0 || d->ld1 % 8 == 0) && d->ldg % 8 == 0 &&
-            (cls || (d->ks <= 3 && d->gs == 1 && d->goff[0] == 0 && d->goff[1] == 0 && d->goff[2] == 0 &&
-                     d->gd == d->do_ && d->gh == d->ho && d->gw == d->wo));
-  if (p->fast) {
-    p->shape = d->wo > 16 ? 0 : 1;
-    p->tiles_d = ceil_div(d->do_, kWTD[p->shape]);
-    p->tiles_h = ceil_div(d->ho, kWTH[p->shape]);
-    p->tiles_w = ceil_div(d->wo, kWTW[p->shape]);
-    p->ntiles = p->tiles_d * p->tiles_h * p->tiles_w * d->n;
-    const int wsl = d->ks == 1 ? 4 : 1;                     // slabs per workgroup
-    // transposed conv at the wide levels: 4 column tiles per workgroup (wgrad_deconv_kernel)
-    p->deconv4 = cls && p->shape == 0 && p->co_tiles % kDeconvNco == 0 && d->do_ % 2 == 0 && d->ho % 4 == 0 && d->wo % 32 == 0;
-    const long long cot = p->deconv4 ? p->co_tiles / kDeconvNco : p->co_tiles;
-    long long sp = tune_wg_target() / ((long long)p->ci_tiles * cot);      // ~2 workgroups per CU (256, 1024 measured slower)
-    if (sp < 1) sp = 1;
-    if (sp > p->ntiles) sp = p->ntiles;
-    while (sp > 1 && sp * wsl * slab_bytes > (256ll << 20)) sp /= 2;
-    p->splits = (int)sp;
-    p->nslabs = d->ks == 1 ? p->splits * 4 : p->splits;
-  }
-  // streaming 1x1x1 kernel: one (ci, co) tile, plain tensors on one grid, many voxels; 32-bit byte offsets
-  p->pw = false;
-  {
-    const long long nv = (long long)d->n * d->di * d->hi * d->wi;
-    if (p->fast && !cls && d->ks == 1 && d->c1 == 0 && d->c0 <= 32 && d->cg <= 32 && d->pad[0] == 0 && d->pad[1] == 0 && d->pad[2] == 0 &&
-        d->di == d->do_ && d->hi == d->ho && d->wi == d->wo && d->s2d_cp == 0 && d->xn == 0 && nv >= (1ll << 17) &&
-        nv * std::max(d->ld0, d->ldg) * 2 < (1ll << 31)) {
-      p->pw = true;
-      p->splits = 256;
-      p->nslabs = 256;
-    }
-  }
-  // marching k2 kernel: dense 2x2x2, padding 0, x one larger than the grid, wide rows; 32-bit byte offsets
-  p->march2 = false;
-  if (p->fast && !cls && d->ks == 2 && d->c1 == 0 && d->pad[0] == 0 && d->pad[1] == 0 && d->pad[2] == 0 && d->di == d->do_ + 1 &&
-      d->hi == d->ho + 1 && d->wi == d->wo + 1 && d->wo >= 32 && d->do_ >= 4 && d->xn == 0 &&
-      (long long)d->n * d->di * d->hi * d->wi * std::max(d->ld0, d->ldg) * 2 < (1ll << 31)) {
-    const int th = ceil_div(d->ho, kW2FH), tw = ceil_div(d->wo, kW2FW);
-    const long long base = (long long)d->n * th * tw * p->ci_tiles * p->co_tiles;
-    long long best = -1; int best_ns = 1;
-    for (int ns = 1; ns <= d->do_ / 2; ++ns) {
-      const int L = ceil_div(d->do_, ns);
-      if ((long long)(ns - 1) * L >= d->do_) continue;
-      const long long wgs = base * ns, cost = ((wgs + 255) / 256) * (L + 3);
-      if ((long long)ns * d->n * th * tw * slab_bytes > (256ll << 20)) break;
-      if (best < 0 || cost < best) { best = cost; best_ns = ns; }
-    }
-    p->march2 = true;
-    p->nseg = best_ns;
-    p->seg_len = ceil_div(d->do_, best_ns);
-    p->tiles_h = th; p->tiles_w = tw;
-    p->nslabs = d->n * th * tw * best_ns;
-  }
-  // marching kernel: 3x3x3, padding 1, same extents, wide rows; 32-bit byte offsets
-  p->march = false;
-  if (p->fast && !cls && d->ks == 3 && d->pad[0] == 1 && d->pad[1] == 1 && d->pad[2] == 1 && d->di == d->do_ && d->hi == d->ho &&
-      d->wi == d->wo && d->wo >= 32 && d->do_ >= 8 &&
-      (long long)d->n * d->di * d->hi * d->wi * std::max(d->ld0, std::max(d->ld1, d->ldg)) * 2 < (1ll << 31)) {
-    const int th = ceil_div(d->ho, kWmFH), tw = ceil_div(d->wo, kWmFW);
-    const long long base = (long long)d->n * th * tw * p->ci_tiles * p->co_tiles;
-    // segments: whole rounds of 256 workgroups (one per CU), cost = rounds x (planes per segment + pipeline fill)
-    long long best = -1; int best_ns = 1;
-    for (int ns = 1; ns <= d->do_ / 4; ++ns) {
-      const int L = ceil_div(d->do_, ns);
-      if ((long long)(ns - 1) * L >= d->do_) continue;
-      const long long wgs = base * ns, cost = ((wgs + 255) / 256) * (L + 3);
-      if ((long long)ns * d->n * th * tw * slab_bytes > (256ll << 20)) break;
-      if (best < 0 || cost < best) { best = cost; best_ns = ns; }
-    }
-    p->march = true;
-    p->nseg = best_ns;
-    p->seg_len = ceil_div(d->do_, best_ns);
-    p->tiles_h = th; p->tiles_w = tw;
-    p->nslabs = d->n * th * tw * best_ns;
+  const bool tile = d->dtype == MI355_DT_BF16 && d->stride == 1 && d->ld0 % 8 == 0 && (d->c1 == 0 || d->ld1 % 8 == 0) && d->ldg % 8 == 0 &&
+                    (cls || (d->ks <= 3 && d->gs == 1 && d->goff[0] == 0 && d->goff[1] == 0 && d->goff[2] == 0 &&
+                             d->gd == d->do_ && d->gh == d->ho && d->gw == d->wo));
+  if (!tile) return MI355_OK;
+  p->kind = kWTile;
+  p->shape = d->wo > 16 ? 0 : 1;
+  p->tiles_d = ceil_div(d->do_, kWTD[p->shape]);
+  p->tiles_h = ceil_div(d->ho, kWTH[p->shape]);
+  p->tiles_w = ceil_div(d->wo, kWTW[p->shape]);
+  p->ntiles = p->tiles_d * p->tiles_h * p->tiles_w * d->n;
+  const int wsl = d->ks == 1 ? 4 : 1;                     // slabs per workgroup
+  // transposed conv at the wide levels: 4 column tiles per workgroup (wgrad_deconv_kernel)
+  p->deconv4 = cls && p->shape == 0 && p->co_tiles % kDeconvNco == 0 && d->do_ % 2 == 0 && d->ho % 4 == 0 && d->wo % 32 == 0;
+  const long long cot = p->deconv4 ? p->co_tiles / kDeconvNco : p->co_tiles;
+  long long sp = tune_wg_target() / ((long long)p->ci_tiles * cot);      // ~2 workgroups per CU (256, 1024 measured slower)
+  if (sp < 1) sp = 1;
+  if (sp > p->ntiles) sp = p->ntiles;
+  while (sp > 1 && sp * wsl * slab_bytes > kSlabCap) sp /= 2;
+  p->splits = (int)sp;
+  p->nslabs = d->ks == 1 ? p->splits * 4 : p->splits;
+  if (cls) return MI355_OK;
+  // the refinements of the tile path address with 32-bit byte offsets
+  const long long nv = (long long)d->n * d->di * d->hi * d->wi;
+  const bool pad0 = d->pad[0] == 0 && d->pad[1] == 0 && d->pad[2] == 0, pad1 = d->pad[0] == 1 && d->pad[1] == 1 && d->pad[2] == 1;
+  if (d->ks == 1 && d->c1 == 0 && d->c0 <= 32 && d->cg <= 32 && pad0 && d->di == d->do_ && d->hi == d->ho && d->wi == d->wo &&
+      d->s2d_cp == 0 && d->xn == 0 && nv >= (1ll << 17) && nv * std::max(d->ld0, d->ldg) * 2 < (1ll << 31)) {
+    // streaming 1x1x1 kernel: one (ci, co) tile, plain tensors on one grid, many voxels
+    p->kind = kWPointwise;
+    p->splits = 256;
+    p->nslabs = 256;
+  } else if (d->ks == 2 && d->c1 == 0 && pad0 && d->di == d->do_ + 1 && d->hi == d->ho + 1 && d->wi == d->wo + 1 && d->wo >= 32 &&
+             d->do_ >= 4 && d->xn == 0 && nv * std::max(d->ld0, d->ldg) * 2 < (1ll << 31)) {
+    // marching k2 kernel: dense 2x2x2, padding 0, x one larger than the grid, wide rows
+    p->kind = kWMarch2;
+    set_wgrad_segments(d, p, ceil_div(d->ho, kW2FH), ceil_div(d->wo, kW2FW), 2, slab_bytes);
+  } else if (d->ks == 3 && pad1 && d->di == d->do_ && d->hi == d->ho && d->wi == d->wo && d->wo >= 32 && d->do_ >= 8 &&
+             nv * std::max(d->ld0, std::max(d->ld1, d->ldg)) * 2 < (1ll << 31)) {
+    // marching kernel: 3x3x3, padding 1, same extents, wide rows
+    p->kind = kWMarch;
+    set_wgrad_segments(d, p, ceil_div(d->ho, kWmFH), ceil_div(d->wo, kWmFW), 4, slab_bytes);
   }
   return MI355_OK;
 }
@@ -1298,7 +1290,7 @@ extern "C" int64_t mi355_conv_wgrad_workspace(const mi355_wgrad_desc* d) {
 extern "C" int mi355_conv_wgrad_plan_kind(const mi355_wgrad_desc* d) {
   WPlan p;
   if (wplan(d, &p)) return -1;
-  return p.march ? 2 : (p.pw ? 3 : (p.march2 ? 4 : (p.fast ? 1 : 0)));
+  return p.kind;
 }
 
 namespace {
@@ -1325,38 +1317,45 @@ int conv_wgrad_impl(const mi355_wgrad_desc* d, mi355_wreduce_job* deferred, void
   a.splits = p.splits; a.tap_groups = p.tap_groups; a.rows = p.rows;
   a.g_cls_cout = d->g_cls_cout;
   a.xn = d->xn > 0 ? d->xn : d->n;
-  MI355_REQUIRE(a.xn == d->n || (!p.march && !(p.fast && p.deconv4)), "wgrad: xn is not supported by this plan");
-  if (p.pw) {
-    const long long nv = (long long)d->n * d->di * d->hi * d->wi;
-    static const int attr = (int)hipFuncSetAttribute((const void*)wgrad_pw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kPwLds);
-    if (attr) { mi355_set_error("wgrad_pw: cannot raise the dynamic LDS limit to %d bytes (hip error %d)", kPwLds, attr); return MI355_ERR_HIP; }
-    wgrad_pw_kernel<<<dim3(256), dim3(256), kPwLds, st>>>(a, nv, (int)((nv + 63) / 64));
-  } else if (p.march2) {
-    const WMarchArgs m{p.seg_len, p.nseg, p.tiles_h, p.tiles_w, p.nslabs, p.ci_tiles, p.co_tiles};
-    static const int attr = (int)hipFuncSetAttribute((const void*)wgrad_march2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kW2Lds);
-    if (attr) { mi355_set_error("wgrad_march2: cannot raise the dynamic LDS limit to %d bytes (hip error %d)", kW2Lds, attr); return MI355_ERR_HIP; }
-    wgrad_march2_kernel<<<dim3(((p.nslabs + 7) / 8) * 8 * p.ci_tiles * p.co_tiles), dim3(256), kW2Lds, st>>>(a, m);
-  } else if (p.march) {
-    const WMarchArgs m{p.seg_len, p.nseg, p.tiles_h, p.tiles_w, p.nslabs, p.ci_tiles, p.co_tiles};
-    static const int attr = (int)hipFuncSetAttribute((const void*)wgrad_march_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kWmLds);
-    if (attr) { mi355_set_error("wgrad_march: cannot raise the dynamic LDS limit to %d bytes (hip error %d)", kWmLds, attr); return MI355_ERR_HIP; }
-    wgrad_march_kernel<<<dim3(((p.nslabs + 7) / 8) * 8 * p.ci_tiles * p.co_tiles), dim3(256), kWmLds, st>>>(a, m);
-  } else if (p.fast && p.deconv4) {
-    const dim3 grid(p.splits, p.ci_tiles, p.co_tiles / kDeconvNco);
-    wgrad_deconv_kernel<<<grid, dim3(256), (1 + kDeconvNco) * 256 * 64, st>>>(a, p.tiles_d, p.tiles_h, p.tiles_w, p.ntiles);
-  } else if (p.fast) {
-    dim3 grid(p.splits, p.ci_tiles, p.co_tiles), block(256);
+  MI355_REQUIRE(a.xn == d->n || (p.kind != kWMarch && !p.deconv4), "wgrad: xn is not supported by this plan");
+  const WMarchArgs m{p.seg_len, p.nseg, p.tiles_h, p.tiles_w, p.nslabs, p.ci_tiles, p.co_tiles};      // (the marching kinds)
+  const dim3 march_grid(((p.nslabs + 7) / 8) * 8 * p.ci_tiles * p.co_tiles);
+  switch (p.kind) {
+    case kWPointwise: {
+      const long long nv = (long long)d->n * d->di * d->hi * d->wi;
+      if ((rc = raise_lds_limit<wgrad_pw_kernel>("wgrad_pw", kPwLds))) return rc;
+      wgrad_pw_kernel<<<dim3(256), dim3(256), kPwLds, st>>>(a, nv, (int)((nv + 63) / 64));
+      break;
+    }
+    case kWMarch2:
+      if ((rc = raise_lds_limit<wgrad_march2_kernel>("wgrad_march2", kW2Lds))) return rc;
+      wgrad_march2_kernel<<<march_grid, dim3(256), kW2Lds, st>>>(a, m);
+      break;
+    case kWMarch:
+      if ((rc = raise_lds_limit<wgrad_march_kernel>("wgrad_march", kWmLds))) return rc;
+      wgrad_march_kernel<<<march_grid, dim3(256), kWmLds, st>>>(a, m);
+      break;
+    case kWTile:
+      if (p.deconv4) {
+        const dim3 grid(p.splits, p.ci_tiles, p.co_tiles / kDeconvNco);
+        wgrad_deconv_kernel<<<grid, dim3(256), (1 + kDeconvNco) * 256 * 64, st>>>(a, p.tiles_d, p.tiles_h, p.tiles_w, p.ntiles);
+      } else {
+        dim3 grid(p.splits, p.ci_tiles, p.co_tiles), block(256);
 #define WG_FAST(KS, TD, TH, TW)                                                                   \
   do {                                                                                            \
     constexpr int lds = ((TD + KS - 1) * (TH + KS - 1) * (TW + KS - 1) + TD * TH * TW) * 64;      \
     wgrad_bf16_kernel<KS, TD, TH, TW><<<grid, block, lds, st>>>(a, p.tiles_d, p.tiles_h, p.tiles_w, p.ntiles); \
   } while (0)
-    if (d->ks == 3) { if (p.shape == 0) WG_FAST(3, 2, 4, 32); else WG_FAST(3, 2, 8, 16); }
-    else if (d->ks == 2) { if (p.shape == 0) WG_FAST(2, 2, 4, 32); else WG_FAST(2, 2, 8, 16); }
-    else { if (p.shape == 0) WG_FAST(1, 2, 4, 32); else WG_FAST(1, 2, 8, 16); }
+        if (d->ks == 3) { if (p.shape == 0) WG_FAST(3, 2, 4, 32); else WG_FAST(3, 2, 8, 16); }
+        else if (d->ks == 2) { if (p.shape == 0) WG_FAST(2, 2, 4, 32); else WG_FAST(2, 2, 8, 16); }
+        else { if (p.shape == 0) WG_FAST(1, 2, 4, 32); else WG_FAST(1, 2, 8, 16); }
 #undef WG_FAST
-  } else if (d->dtype == MI355_DT_F32) launch_wgrad<float>(a, p, st);
-  else launch_wgrad<bf16_t>(a, p, st);
+      }
+      break;
+    default:      // kWGeneric
+      if (d->dtype == MI355_DT_F32) launch_wgrad<float>(a, p, st);
+      else launch_wgrad<bf16_t>(a, p, st);
+  }
   rc = mi355_check_launch("conv_wgrad");
   if (rc) return rc;
   RedJob job;

@@ -5,7 +5,7 @@ PyTorch is used for device memory and streams only."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -243,19 +243,52 @@ def conv_num_tiles(x0, x1, wp, coutp, ks, stride, pad, out, grid, os=1, ooff=(0,
     return tiles.value, tps.value
 
 
+class PlanId(NamedTuple):
+    """mi355_conv_plan_id = 10000 ks + 1000 halo + 100 shape + 10 vt + ct, taken apart."""
+    ks: int
+    halo: int       # 1: a halo-tile / marching kernel (`shape` names the family), 0: a gather / pointwise kernel (shape 0)
+    shape: int
+    vt: int
+    ct: int
+
+
+# kernel families of the halo plans that Python asks about (ConvShape in csrc/conv_api.hip)
+SHAPE_RU, SHAPE_MARCH, SHAPE_MARCHG, SHAPE_LOWG_W16, SHAPE_LOWG_W8, SHAPE_MARCH2 = 9, 10, 11, 12, 13, 14
+SHAPES_LOWG = (SHAPE_LOWG_W16, SHAPE_LOWG_W8)
+
+
+def decode_plan_id(pid: int) -> PlanId:
+    assert pid > 0, pid
+    ks, rest = divmod(pid, 10000)
+    halo = 1 if rest >= 1000 else 0                 # (shapes reach 14, so the halo flag and the shape share the thousands)
+    return PlanId(ks, halo, (rest - 1000 * halo) // 100, (rest % 100) // 10, rest % 10)
+
+
+def _probe_desc(n, in_extents, grid, c_in, coutp, ks, pad, dtype, y_extents=None, ldy=None, cstore=None, ptr=256):
+    """Descriptor of a stride-1 convolution of one plain (n, *in_extents, c_in) tensor for planner queries only: no launch,
+    the planner only checks pointers for null, so they all hold `ptr`."""
+    d = _lib.ConvDesc()
+    d.x0, d.c0, d.ld0 = ptr, c_in, c_in
+    d.n = n
+    d.di, d.hi, d.wi = in_extents
+    d.do_, d.ho, d.wo = grid
+    d.dy, d.hy, d.wy = grid if y_extents is None else y_extents
+    d.ks, d.stride, d.os = ks, 1, 1
+    d.pad = (C.c_int32 * 3)(pad, pad, pad)
+    d.wp, d.coutp = ptr, coutp
+    d.y, d.ldy, d.cstore = ptr, (coutp if ldy is None else ldy), (coutp if cstore is None else cstore)
+    d.dtype = dtype
+    if dtype == DT_FP8:
+        d.q_amax_x = d.q_amax_w = ptr
+    return d
+
+
 def conv_k2_marches(n: int, s_extents, c_in: int, coutp: int) -> bool:
     """Would a bf16 dense k2 (padding 0) convolution of an (n, *s_extents, c_in) space-to-depth tensor to coutp channels run
     on conv_march2_kernel -- the plan that honours `addend` / an f32 output?  (Asked before a layer is split.)"""
-    d = _lib.ConvDesc()
-    d.x0, d.c0, d.ld0, d.n = 1, c_in, c_in, n                # (no launch: the planner only checks for non-null pointers)
-    d.di, d.hi, d.wi = s_extents
-    d.do_, d.ho, d.wo = (e - 1 for e in s_extents)
-    d.dy, d.hy, d.wy = d.do_, d.ho, d.wo
-    d.ks, d.stride, d.os = 2, 1, 1
-    d.wp, d.coutp, d.y, d.ldy, d.cstore = 1, coutp, 1, coutp, coutp
-    d.dtype = DT_BF16
+    d = _probe_desc(n, s_extents, tuple(e - 1 for e in s_extents), c_in, coutp, 2, 0, DT_BF16)
     pid = _lib.load().mi355_conv_plan_id(C.byref(d))
-    return pid > 0 and (pid % 10000) // 100 == 24          # 10000 ks + 1000 halo + 100 shape + ...: halo plan, shape 14
+    return pid > 0 and decode_plan_id(pid)[1:3] == (1, SHAPE_MARCH2)
 
 
 # Optional launch probe (bench.py): called as probe(plan_id, desc, (cin, cout) real GEMM extents) and returns None or a callable
@@ -466,21 +499,8 @@ def conv_fp8_layer_ok(n: int, d: int, h: int, w: int, c_in: int, c_out: int) -> 
     key = (n, d, h, w, c_in, c_out)
     hit = _FP8_OK.get(key)
     if hit is None:
-        d_ = _lib.ConvDesc()
-        d_.x0, d_.c0, d_.ld0 = 256, c_in, c_in
-        d_.x1, d_.c1, d_.ld1 = None, 0, 0
-        d_.n, d_.di, d_.hi, d_.wi = n, d, h, w
-        d_.do_, d_.ho, d_.wo = d, h, w
-        d_.ks, d_.stride = 3, 1
-        d_.pad = (C.c_int32 * 3)(1, 1, 1)
-        d_.wp, d_.coutp = 256, round_up(c_out, 32)
         co = round_up(c_out, 16)
-        d_.y, d_.ldy, d_.cstore = 256, co, co
-        d_.dy, d_.hy, d_.wy = d, h, w
-        d_.os = 1
-        d_.ooff = (C.c_int32 * 3)(0, 0, 0)
-        d_.dtype = DT_FP8
-        d_.q_amax_x = d_.q_amax_w = 256
+        d_ = _probe_desc(n, (d, h, w), (d, h, w), c_in, round_up(c_out, 32), 3, 1, DT_FP8, ldy=co, cstore=co)
         hit = _FP8_OK[key] = _lib.load().mi355_conv_plan_id(C.byref(d_)) > 0
     return hit
 
@@ -494,20 +514,8 @@ def conv_fp8_supported(x0: torch.Tensor, coutp: int, out: torch.Tensor, grid) ->
     n, di, hi, wi, c0 = x0.shape
     if c0 != 32 or not x0.is_cuda:
         return False
-    d = _lib.ConvDesc()
-    d.x0, d.c0, d.ld0 = x0.data_ptr(), c0, c0
-    d.x1, d.c1, d.ld1 = None, 0, 0
-    d.n, d.di, d.hi, d.wi = n, di, hi, wi
-    d.do_, d.ho, d.wo = grid
-    d.ks, d.stride = 3, 1
-    d.pad = (C.c_int32 * 3)(1, 1, 1)
-    d.wp, d.coutp = x0.data_ptr(), coutp
-    d.y, d.ldy, d.cstore = out.data_ptr(), act_ld(out), out.shape[4]
-    d.dy, d.hy, d.wy = out.shape[1:4]
-    d.os = 1
-    d.ooff = (C.c_int32 * 3)(0, 0, 0)
-    d.dtype = DT_FP8
-    d.q_amax_x = d.q_amax_w = x0.data_ptr()
+    d = _probe_desc(n, (di, hi, wi), grid, c0, coutp, 3, 1, DT_FP8, y_extents=out.shape[1:4], ldy=act_ld(out), cstore=out.shape[4],
+                    ptr=x0.data_ptr())
     return _lib.load().mi355_conv_plan_id(C.byref(d)) > 0
 
 
