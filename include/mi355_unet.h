@@ -668,7 +668,7 @@ typedef struct mi355_scalar_table { const float* src[MI355_EPOCH_MAX_SCALARS]; }
 int mi355_epoch_accumulate(const mi355_scalar_table* table, int32_t n, double weight, double* acc, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * MedicalNet ResNet-10 feature extractor, FORWARD ONLY -- the frozen network inside the reference's
+ * MedicalNet ResNet-10 feature extractor, forward (the backward follows below) -- the frozen network inside the reference's
  * Perceptual term (src/model.py:123-138) and behind its FID metric (:158-163, 235-257).  Eval mode: every BatchNorm is folded
  * into its convolution by the caller (w' = w g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps), in f32, before the
  * weights are rounded to bf16).  Activations are DENSE bf16 NDHWC (ld == C), 16-byte aligned; bias is f32; f32 accumulation.
@@ -706,6 +706,45 @@ int64_t mi355_medicalnet_tail_workspace_bytes(int32_t items, int32_t c, int32_t 
 int mi355_medicalnet_tail(const void* feat_pred, const void* feat_target, int32_t items, int32_t c, int32_t vox,
                           void* workspace, int64_t workspace_bytes, float* mean_pred, float* mean_target, float* item_sum,
                           float* value, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Backward of the Perceptual term with respect to the PREDICTION (csrc/medicalnet_bwd.hip).  The network is
+ * frozen and the target constant: data gradients only.  Gradients between layers are dense bf16 NDHWC like the activations;
+ * f32 accumulation, one rounding at the store.  Every element of every output is written, zeros included.
+ *   mi355_medicalnet_tail_bwd    : g_feat = d value / d feat_pred * g_out[0] * [feat_pred > 0], in the layout of feat_pred.
+ *                                  g_out: one float in DEVICE memory.  A voxel whose prediction features are all zero gets zeros.
+ *   mi355_medicalnet_dgrad       : dx[i, ci] = sum_tap sum_co dy[(i + pad - tap dilation) / stride, co] w[co, ci, tap] over the
+ *                                  taps whose division is exact and whose quotient is in range; then + add (may be NULL, shape
+ *                                  of dx), then zero where mask <= 0 (a saved activation of the shape of dx, may be NULL).
+ *                                  d, h, w: extents of dx (the convolution's INPUT); dy has (n - 1) / stride + 1 per axis.
+ *                                  Shapes as mi355_medicalnet_conv; anything else returns MI355_ERR_UNSUPPORTED.
+ *                                  wp: bf16 [ks^3][cout / 16][cin][16], element (tap, q, ci, e) = w[16 q + e][ci][kd][kh][kw].
+ *   mi355_medicalnet_maxpool_bwd : dx = [x > 0] * (MaxPool3d(k3, s2, p1) backward of dy at x); ties go to the first maximum
+ *                                  of a window in (d, h, w) scan order.  d, h, w, c: shape of x.  workspace: one byte per
+ *                                  element of dy (the windows' arg-max taps), 16-byte aligned.
+ *   mi355_medicalnet_stem_dgrad  : g[s][i] = sum_co sum_k dy[(i + 3 - k) / 2, co] w[co][k] (k7, s2, p3), f32 in the layout of x,
+ *                                  and part[2 b], part[2 b + 1] = workgroup b's f64 sums of g and of g * (x - mean) / std,
+ *                                  b < mi355_medicalnet_stem_dgrad_blocks(samples, d, h, w).
+ *                                  wp: bf16 [64][2][8][32], element (t, half, cls, e) = w[32 half + e][kd][kh][kw] with, per
+ *                                  axis, k = p + 5 - 2 a for offset a of t = (ad * 4 + ah) * 4 + aw and parity p of
+ *                                  cls = 4 pd + 2 ph + pw; zero where a k falls outside 0..6.
+ *   mi355_medicalnet_norm_bwd    : dv = (g - sum g / n - x^ sum(g x^) / (n - 1)) / std, x^ = (x - mean) / std: the gradient
+ *                                  through (v - v.mean()) / v.std() over the whole tensor (unbiased std).  nb partial pairs.
+ * No atomics, fixed reduction orders (two calls give identical bits), no host read: the calls record into a hipGraph.
+ * ---------------------------------------------------------------------------------------- */
+int mi355_medicalnet_tail_bwd(const void* feat_pred, const void* feat_target, const float* g_out, void* g_feat, int32_t items,
+                              int32_t c, int32_t vox, void* stream);
+int mi355_medicalnet_dgrad(const void* dy, const void* wp, const void* add, const void* mask, void* dx, int32_t samples,
+                           int32_t d, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t ks, int32_t stride,
+                           int32_t dilation, void* stream);
+int64_t mi355_medicalnet_maxpool_bwd_workspace_bytes(int32_t samples, int32_t d, int32_t h, int32_t w, int32_t c);
+int mi355_medicalnet_maxpool_bwd(const void* x, const void* dy, void* workspace, int64_t workspace_bytes, void* dx,
+                                 int32_t samples, int32_t d, int32_t h, int32_t w, int32_t c, void* stream);
+int32_t mi355_medicalnet_stem_dgrad_blocks(int32_t samples, int32_t d, int32_t h, int32_t w);
+int mi355_medicalnet_stem_dgrad(const void* dy, const void* wp, const float* x, const float* mean_std, float* g, double* part,
+                                int32_t samples, int32_t d, int32_t h, int32_t w, void* stream);
+int mi355_medicalnet_norm_bwd(const float* g, const float* x, const float* mean_std, const double* part, int32_t nb, float* dv,
+                              int64_t n, void* stream);
 
 /* layout probe used by the tests: writes lane -> (row, col) maps of the MFMA accumulators */
 int mi355_mfma_selftest(float* out_f32_1024, float* out_bf16_1024, void* stream);

@@ -4,6 +4,10 @@ stock torch in bf16 (channels-last Conv3d + eval BatchNorm3d modules) on the sam
 rounds in one process; one JSON line per measurement (median and min over the rounds, ms).
 
     python tools/bench_perceptual.py [--parts ours,stock] [--reps 10] [--batch 8] [--channels 6] [--size 64]
+
+``--parts backward,stock_backward`` measures the backward with respect to the prediction the same way: whole and by part (tail,
+every block's data-gradient launches, pool, stem, normalisation), a data gradient counted with its forward's FLOPs, next to the
+same network's backward with respect to its input in stock torch (bf16, channels-last, autograd).
 """
 import argparse
 import copy
@@ -19,7 +23,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from unet_bssfp_amd import ops                                           # noqa: E402
 from unet_bssfp_amd.losses import PerceptualLoss                         # noqa: E402
-from unet_bssfp_amd.medicalnet import BLOCKS, MedicalNetResNet10         # noqa: E402
+from unet_bssfp_amd.medicalnet import BLOCKS, MedicalNetResNet10, medicalnet_backward   # noqa: E402
 
 PEAK_BF16_FLOPS = 2.5e15                                                 # MI355X dense bf16 MFMA (spec)
 
@@ -147,6 +151,93 @@ def bench_stock(net, pred, reps):
         return report("stock_torch_bf16", rounds(fns, reps, warmup=2), flops)
 
 
+def bench_backward(net, pred, target, reps):
+    """the differentiable term: forward with the activations kept, backward whole and by part"""
+    b, c = pred.shape[:2]
+    samples = b * c
+    flops = conv_flops(samples, pred.shape[2])
+    p = net.packed()
+    term = PerceptualLoss(net, differentiable=True, factor=1e3)
+    leaf = pred.clone().requires_grad_()
+    up = torch.ones((), device=pred.device)
+    kept = {}
+    fp, ft = net.features(pred, keep=kept), net.features(target)
+    g_out = torch.full((1,), 1e3, device=pred.device)
+    vols = pred.view(samples, *pred.shape[2:])
+    holder = {}
+
+    def fwd_bwd():
+        torch.autograd.grad(term(leaf, target), leaf, up)
+
+    def backward_only():
+        if "v" not in holder:
+            holder["v"] = term(leaf, target)
+        torch.autograd.grad(holder["v"], leaf, up, retain_graph=True)
+
+    def whole():
+        return medicalnet_backward(net, pred, kept, ops.medicalnet_tail_bwd(fp, ft, g_out, b, c))
+    fns = {"forward_keep_plus_backward": fwd_bwd, "backward": backward_only, "backward_launches": whole,
+           "tail_bwd": lambda: ops.medicalnet_tail_bwd(fp, ft, g_out, b, c)}
+    g = ops.medicalnet_tail_bwd(fp, ft, g_out, b, c)
+    inputs = (kept["pool"],) + tuple(kept[f"{name}.out"] for name, *_ in BLOCKS[:-1])
+    for k in range(len(BLOCKS) - 1, -1, -1):
+        name, _cin, _cout, stride, dil = BLOCKS[k]
+
+        def block(g=g, name=name, stride=stride, dil=dil, a_in=inputs[k], k=k):
+            g_t = ops.medicalnet_dgrad(g, p[f"{name}.conv2.dw"], kept[f"{name}.t"].shape, 3, 1, dil, mask=kept[f"{name}.t"])
+            r = ops.medicalnet_dgrad(g, p[f"{name}.down.dw"], a_in.shape, 1, stride, 1) if f"{name}.down.dw" in p else g
+            return ops.medicalnet_dgrad(g_t, p[f"{name}.conv1.dw"], a_in.shape, 3, stride, dil, add=r, mask=a_in if k > 0 else None)
+        fns[name + "_bwd"] = block
+        flops[name + "_bwd"] = flops[name]
+        g = block()
+    g_pool = g
+    g_stem = ops.medicalnet_maxpool_bwd(kept["stem"], g_pool)
+    g_hat, part = ops.medicalnet_stem_dgrad(g_stem, p["stem.dw"], vols, kept["mean_std"])
+    fns["maxpool_bwd"] = lambda: ops.medicalnet_maxpool_bwd(kept["stem"], g_pool)
+    fns["stem_bwd"] = lambda: ops.medicalnet_stem_dgrad(g_stem, p["stem.dw"], vols, kept["mean_std"])
+    fns["norm_bwd"] = lambda: ops.medicalnet_norm_bwd(g_hat, vols, kept["mean_std"], part)
+    flops["stem_bwd"] = flops["stem"]
+    total = sum(flops[k] for k in ("stem",) + tuple(n for n, *_ in BLOCKS))
+    flops.update(backward=total, backward_launches=total, forward_keep_plus_backward=3 * total)
+    return report("hip_backward", rounds(fns, reps), flops)
+
+
+def bench_stock_backward(net, pred, reps):
+    """the same network's backward with respect to its input as stock torch autograd, bf16, channels-last, part by part"""
+    m = copy.deepcopy(net).to(torch.bfloat16).to(memory_format=torch.channels_last_3d)
+    x = ((pred - pred.mean()) / pred.std()).view(-1, 1, *pred.shape[2:]).to(torch.bfloat16).contiguous(memory_format=torch.channels_last_3d)
+
+    def stem(x):
+        return F.relu(m.bn1(m.conv1(x)))
+
+    def block(blk, x):
+        out = blk.bn2(blk.conv2(F.relu(blk.bn1(blk.conv1(x)))))
+        return F.relu(out + (x if blk.downsample is None else blk.downsample(x)))
+
+    def part(fn, x):
+        """backward of one part alone: its forward graph is built once and kept"""
+        leaf = x.detach().clone().requires_grad_()
+        y = fn(leaf)
+        gy = torch.randn_like(y)
+        return y.detach(), (lambda: torch.autograd.grad(y, leaf, gy, retain_graph=True))
+    fns = {}
+    s, fns["stem_bwd"] = part(stem, x)
+    a, fns["maxpool_bwd"] = part(lambda t: F.max_pool3d(t, 3, 2, 1), s)
+    for name, *_ in BLOCKS:
+        a, fns[name + "_bwd"] = part(lambda t, blk=getattr(m, name)[0]: block(blk, t), a)
+
+    def whole(t):
+        t = F.max_pool3d(stem(t), 3, 2, 1)
+        for name, *_ in BLOCKS:
+            t = block(getattr(m, name)[0], t)
+        return t
+    _, fns["backward"] = part(whole, x)
+    flops = conv_flops(x.shape[0], x.shape[2])
+    flops = {k + "_bwd": v for k, v in flops.items()}
+    flops["backward"] = sum(flops.values())
+    return report("stock_torch_bf16_backward", rounds(fns, reps, warmup=2), flops)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="ours,stock")
@@ -172,3 +263,11 @@ if __name__ == "__main__":
     if ours and stock:
         keys = [k for k in stock if k in ours]
         print(json.dumps(dict(what="hip_over_stock", **{k: round(ours[k] / stock[k], 3) for k in keys})), flush=True)
+    ours = stock = None
+    if "backward" in parts:
+        ours = bench_backward(net, pred, target, a.reps)
+    if "stock_backward" in parts:
+        stock = bench_stock_backward(net, pred, a.reps)
+    if ours and stock:
+        keys = [k for k in stock if k in ours]
+        print(json.dumps(dict(what="hip_over_stock_backward", **{k: round(ours[k] / stock[k], 3) for k in keys})), flush=True)

@@ -179,6 +179,13 @@ _SIGNATURES = {
     "mi355_medicalnet_conv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mi355_medicalnet_tail_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "mi355_medicalnet_tail": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mi355_medicalnet_tail_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "mi355_medicalnet_dgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mi355_medicalnet_maxpool_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "mi355_medicalnet_maxpool_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mi355_medicalnet_stem_dgrad_blocks": (_i32, [_i32, _i32, _i32, _i32]),
+    "mi355_medicalnet_stem_dgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mi355_medicalnet_norm_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     "mi355_mfma_selftest": (C.c_int, [_vp, _vp, _vp]),
     "mi355_amax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "mi355_amax_act": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _vp, _vp]),

@@ -1392,6 +1392,32 @@ class SSIM3dFn(Function):
         return ops.ssim3d_loss_bwd(a, b, p, g, ctx.window), None, None, None, None
 
 
+class PerceptualFn(Function):
+    """The MedicalNet Perceptual distance of contiguous f32 (B, C, D, H, W) tensors, f32 (), differentiable in ``y_hat`` only
+    (losses.PerceptualLoss(differentiable=True)).  The forward is the extractor and tail pass of the metric path -- the same
+    launches, so the same bits -- with the prediction's activations kept; the target's run keeps nothing.  The incoming
+    gradient stays on the device (ops.medicalnet_tail_bwd), so a step with this term captures into a hipGraph."""
+
+    @staticmethod
+    def forward(ctx, y_hat, y, net):
+        kept = {}
+        fp, ft = net.features(y_hat, keep=kept), net.features(y)
+        value, _item_sum, _mp, _mt = ops.medicalnet_tail(fp, ft, y_hat.shape[0], y_hat.shape[1])
+        ctx.net, ctx.names = net, tuple(kept)
+        ctx.save_for_backward(y_hat, ft, *kept.values())
+        return value.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from .medicalnet import medicalnet_backward
+        y_hat, ft, *saved = ctx.saved_tensors
+        kept = dict(zip(ctx.names, saved))
+        fp = kept["layer4.out"]
+        g_feat = ops.medicalnet_tail_bwd(fp, ft, g.to(torch.float32).reshape(1).contiguous(), y_hat.shape[0], y_hat.shape[1])
+        return medicalnet_backward(ctx.net, y_hat, kept, g_feat), None, None
+
+
 class GanGenLossFn(Function):
     """The generator phase's loss head (src/model.py:126-137) as one launch each way on top of the L1 kernels:
     (adv + recon, [L1, recon, adv, adv + recon]) with adv = BCEWithLogits(logits, 1).mean() and recon = L1(y_hat, y) / divisor

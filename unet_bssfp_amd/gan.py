@@ -11,10 +11,11 @@
   by the caller (no host sync inside the step)
 * DDP gradient all-reduce                         -> ``GradSync`` hooks (``ddp.py``), one per network
 
-The Perceptual term (src/model.py:127-129) runs on the MedicalNet ResNet-10 (``medicalnet.py``).  Its
-forward is built, its backward is absent: with ``medicalnet=net`` the model logs the Perceptual distance
-and FID as validation / test metrics, and the training objective is unchanged -- the term stays out of
-the pluggable slot (``extra_recon_terms``), as stated wherever numbers are reported.  The module is
+The Perceptual term (src/model.py:127-129) runs on the MedicalNet ResNet-10 (``medicalnet.py``), forward
+and backward with respect to the prediction.  With ``medicalnet=net`` the model logs the Perceptual distance
+and FID as validation / test metrics.  The training objective is unchanged by default: the term enters it
+through the pluggable slot, ``extra_recon_terms=losses.reference_recon_terms(net)``, which gives the
+reference's ``(L1 + 1e3 Perceptual) / 2 * recon_factor``; numbers state which objective they ran.  The module is
 agnostic of where ``gen``/``discr`` come from, so the same step logic drives the CPU oracle modules in
 the tests.
 """

@@ -5,11 +5,13 @@ averages the terms of the slot).  ``SSIMLoss`` has the constructor signature of 
 absent from this image, so parity with it is UNPINNED, as for ``metrics.SSIMMetric``: the formulas are the ones restated
 in oracle/metrics_ref.py, and the tests check value and gradient against that oracle in f64.
 
-``PerceptualLoss`` is the VALUE of the MedicalNet Perceptual term on the frozen ResNet-10 of ``medicalnet.py`` (weights:
+``PerceptualLoss`` is the MedicalNet Perceptual term on the frozen ResNet-10 of ``medicalnet.py`` (weights:
 ``checkpoint.medicalnet_state_dict``; parity with MONAI's ``PerceptualLoss(network_type="medicalnet_resnet10_23datasets")``
-unpinned for the same reason).  Its forward is built, its backward is ABSENT: it serves as a validation / test quantity and
-refuses tensors that require grad, so it cannot sit in ``extra_recon_terms`` of a training step yet.
+unpinned for the same reason).  By default it is the VALUE only, a validation / test quantity that refuses tensors that
+require grad.  ``differentiable=True`` adds the gradient with respect to the prediction (csrc/medicalnet_bwd.hip), and
+``reference_recon_terms(net)`` is the slot content that makes the reference's objective (src/model.py:201-213):
 
+    model = bSSFPToDWITensorModel("bssfp", extra_recon_terms=reference_recon_terms(net))   # (L1 + 1e3 Perceptual) / 2 * recon_factor
     model = bSSFPToDWITensorModel("bssfp", extra_recon_terms={"SSIM": SSIMLoss(3)})   # recon = (L1 + SSIM) / 2 * recon_factor
 """
 from __future__ import annotations
@@ -18,7 +20,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .functional import SSIM3dFn
+from .functional import PerceptualFn, SSIM3dFn
 from .medicalnet import MedicalNetResNet10, medicalnet_distances
 
 
@@ -67,31 +69,49 @@ class SSIMLoss(nn.Module):
 
 
 class PerceptualLoss(nn.Module):
-    """The reference's Perceptual distance (MONAI ``MedicalNetPerceptualSimilarity``, ``channel_wise=False``), forward only.
+    """The reference's Perceptual distance (MONAI ``MedicalNetPerceptualSimilarity``, ``channel_wise=False``) times ``factor``.
 
     Prediction and target are each normalised over the whole tensor, every channel runs through the ResNet-10 as its own
     volume, the C outputs are concatenated to (B, 512 C, d, h, w), and with f^ = f / (sqrt(sum_ch f^2) + 1e-10) the value is
-    the mean over batch and positions of sum_ch (f^_input - f^_target)^2.  The model multiplies it by ``perceptual_factor``.
-    The whole forward stays on the device (no host read), so it records into a hipGraph.  There is no backward: an
-    ``input`` or ``target`` that requires grad raises ``NotImplementedError``."""
+    the mean over batch and positions of sum_ch (f^_input - f^_target)^2.  The whole computation stays on the device (no host
+    read), so it records into a hipGraph.
 
-    def __init__(self, net: MedicalNetResNet10, spatial_dims: int = 3):
+    ``differentiable=False`` (the default): the value only; an ``input`` or ``target`` that requires grad raises
+    ``NotImplementedError``.  ``differentiable=True``: the same value, bit for bit, with the gradient with respect to
+    ``input`` (``functional.PerceptualFn``); a ``target`` that requires grad is refused, as by ``SSIMLoss``."""
+
+    def __init__(self, net: MedicalNetResNet10, spatial_dims: int = 3, differentiable: bool = False, factor: float = 1.0):
         super().__init__()
         if spatial_dims != 3:
             raise NotImplementedError("only the reference's 3-D configuration is built")
         self._net = (net,)                                            # not a submodule: the frozen network is shared, not owned
+        self.differentiable, self.factor = bool(differentiable), float(factor)
 
     @property
     def net(self) -> MedicalNetResNet10:
         return self._net[0]
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        if input.requires_grad or target.requires_grad:
-            raise NotImplementedError("PerceptualLoss: only the forward is built; the backward pass through the MedicalNet "
-                                      "ResNet-10 is missing, so the term cannot be trained on -- detach both tensors")
+        if not self.differentiable and (input.requires_grad or target.requires_grad):
+            raise NotImplementedError("PerceptualLoss: this instance computes the value only, without the backward pass through "
+                                      "the MedicalNet ResNet-10 -- detach both tensors, or pass differentiable=True to train on "
+                                      "the term")
+        if target.requires_grad:
+            raise NotImplementedError("only the gradient with respect to `input` is built; detach `target`")
         if not (input.is_cuda and target.is_cuda):
             raise _lib.Mi355Error("PerceptualLoss runs on the GPU only (no CPU fallback)")
         if input.dim() != 5:
             raise ValueError(f"input should have 5 dimensions (batch, channel, D, H, W), got {input.dim()}.")
-        value, _, _ = medicalnet_distances(self.net, input, target)
-        return value.reshape(())
+        if self.differentiable:
+            if input.shape != target.shape:
+                raise ValueError(f"input and target should have same shapes, got {tuple(input.shape)} and {tuple(target.shape)}.")
+            value = PerceptualFn.apply(input.float().contiguous(), target.detach().float().contiguous(), self.net)
+        else:
+            value = medicalnet_distances(self.net, input, target)[0].reshape(())
+        return value if self.factor == 1.0 else value * self.factor
+
+
+def reference_recon_terms(net: MedicalNetResNet10, perceptual_factor: float = 1e3):
+    """``extra_recon_terms`` of the reference's objective: with it ``recon = (L1 + perceptual_factor * Perceptual) / 2 *
+    recon_factor`` (src/model.py:201-213; the default ``recon_divisor`` then counts the two terms)."""
+    return {"Perceptual": PerceptualLoss(net, differentiable=True, factor=perceptual_factor)}

@@ -992,7 +992,7 @@ def mfma_selftest(device) -> Tuple[torch.Tensor, torch.Tensor]:
     return a.view(32, 32), b.view(32, 32)
 
 
-# ---------------------------------------------------------------------------------------------- MedicalNet ResNet-10 (forward only)
+# ---------------------------------------------------------------------------------------------- MedicalNet ResNet-10
 def _out_extent(n: int, stride: int) -> int:
     return (n - 1) // stride + 1
 
@@ -1077,3 +1077,84 @@ def medicalnet_tail(feat_pred: torch.Tensor, feat_target: torch.Tensor, items: i
                                          mp.data_ptr(), mt.data_ptr(), item_sum.data_ptr(), value.data_ptr(), _stream()),
                "medicalnet_tail")
     return value, item_sum, mp, mt
+
+
+# ---- backward of the Perceptual term with respect to the prediction (csrc/medicalnet_bwd.hip) ----
+def medicalnet_tail_bwd(feat_pred: torch.Tensor, feat_target: torch.Tensor, g_out: torch.Tensor, items: int,
+                        channels: int) -> torch.Tensor:
+    """d value / d feat_pred * g_out * [feat_pred > 0] as bf16 in the layout of feat_pred; g_out: one f32 on the device"""
+    _bf16_act(feat_pred, "medicalnet_tail_bwd")
+    _bf16_act(feat_target, "medicalnet_tail_bwd")
+    require_cuda(g_out)
+    assert feat_pred.shape == feat_target.shape and feat_pred.shape[0] == items * channels and feat_pred.shape[4] == 512
+    assert g_out.dtype == torch.float32 and g_out.numel() == 1
+    vox = feat_pred.shape[1] * feat_pred.shape[2] * feat_pred.shape[3]
+    gf = new_act(*feat_pred.shape, torch.bfloat16, feat_pred.device)
+    _lib.check(_lib.load().mi355_medicalnet_tail_bwd(feat_pred.data_ptr(), feat_target.data_ptr(), g_out.data_ptr(), gf.data_ptr(),
+                                                     items, channels, vox, _stream()), "medicalnet_tail_bwd")
+    return gf
+
+
+def medicalnet_dgrad(dy: torch.Tensor, wp: torch.Tensor, in_shape: Sequence[int], ks: int = 3, stride: int = 1, dilation: int = 1,
+                     add: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Data gradient of ``medicalnet_conv``: dy bf16 (S, D', H', W', cout) -> bf16 ``in_shape`` = (S, D, H, W, cin), + ``add``,
+    zeroed where the saved activation ``mask`` is <= 0.  wp: bf16 [ks^3][cout / 16][cin][16] (medicalnet.pack_dgrad_weight)."""
+    _bf16_act(dy, "medicalnet_dgrad")
+    require_cuda(wp, add, mask)
+    s, d, h, w, cin = (int(v) for v in in_shape)
+    cout = dy.shape[4]
+    assert dy.shape[0] == s and tuple(dy.shape[1:4]) == tuple(_out_extent(n, stride) for n in (d, h, w)), (tuple(dy.shape), in_shape)
+    assert wp.dtype == torch.bfloat16 and wp.is_contiguous() and wp.numel() == ks ** 3 * cin * cout
+    dx = new_act(s, d, h, w, cin, torch.bfloat16, dy.device)
+    for t, what in ((add, "add"), (mask, "mask")):
+        if t is not None:
+            _bf16_act(t, f"medicalnet_dgrad {what}")
+            assert t.shape == dx.shape
+    _lib.check(_lib.load().mi355_medicalnet_dgrad(dy.data_ptr(), wp.data_ptr(), _ptr(add), _ptr(mask), dx.data_ptr(), s, d, h, w,
+                                                  cin, cout, ks, stride, dilation, _stream()), "medicalnet_dgrad")
+    return dx
+
+
+def medicalnet_maxpool_bwd(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+    """[x > 0] * backward of MaxPool3d(k3, s2, p1) at the bf16 (S, D, H, W, C) tensor x; ties: first maximum in scan order"""
+    _bf16_act(x, "medicalnet_maxpool_bwd")
+    _bf16_act(dy, "medicalnet_maxpool_bwd")
+    s, d, h, w, c = x.shape
+    assert tuple(dy.shape) == (s, _out_extent(d, 2), _out_extent(h, 2), _out_extent(w, 2), c)
+    lib = _lib.load()
+    need = lib.mi355_medicalnet_maxpool_bwd_workspace_bytes(s, d, h, w, c)
+    work = new_act(*dy.shape, torch.uint8, x.device)               # one arg-max tap per element of dy
+    assert work.numel() == need
+    dx = new_act(s, d, h, w, c, torch.bfloat16, x.device)
+    _lib.check(lib.mi355_medicalnet_maxpool_bwd(x.data_ptr(), dy.data_ptr(), work.data_ptr(), need, dx.data_ptr(), s, d, h, w, c,
+                                                _stream()), "medicalnet_maxpool_bwd")
+    return dx
+
+
+def medicalnet_stem_dgrad(dy: torch.Tensor, wp: torch.Tensor, x: torch.Tensor, mean_std: torch.Tensor):
+    """dy: bf16 (S, D', H', W', 64), x: the f32 (S, D, H, W) volumes of the forward -> (g f32 like x, the gradient with respect
+    to the normalised input; part f64 (blocks, 2): partial sums of g and of g * (x - mean) / std)"""
+    _bf16_act(dy, "medicalnet_stem_dgrad")
+    require_cuda(wp, x, mean_std)
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+    s, d, h, w = x.shape
+    assert tuple(dy.shape) == (s, _out_extent(d, 2), _out_extent(h, 2), _out_extent(w, 2), 64)
+    assert wp.dtype == torch.bfloat16 and wp.numel() == 64 * 2 * 8 * 32 and wp.is_contiguous()
+    assert mean_std.dtype == torch.float32 and mean_std.numel() == 2
+    lib = _lib.load()
+    g = new_act(s, d, h, w, 1, torch.float32, x.device).view(s, d, h, w)          # one channel: NDHWC is NCDHW
+    part = new_act(1, 1, 1, lib.mi355_medicalnet_stem_dgrad_blocks(s, d, h, w), 2, torch.float64, x.device).view(-1, 2)
+    _lib.check(lib.mi355_medicalnet_stem_dgrad(dy.data_ptr(), wp.data_ptr(), x.data_ptr(), mean_std.data_ptr(), g.data_ptr(),
+                                               part.data_ptr(), s, d, h, w, _stream()), "medicalnet_stem_dgrad")
+    return g, part
+
+
+def medicalnet_norm_bwd(g: torch.Tensor, x: torch.Tensor, mean_std: torch.Tensor, part: torch.Tensor) -> torch.Tensor:
+    """the gradient through (v - v.mean()) / v.std() over the whole tensor x, given g = d / d normalised and its partial sums"""
+    require_cuda(g, x, mean_std, part)
+    assert g.dtype == x.dtype == torch.float32 and g.is_contiguous() and x.is_contiguous() and g.shape == x.shape and x.dim() == 4
+    assert part.dtype == torch.float64 and part.is_contiguous() and part.dim() == 2 and part.shape[1] == 2
+    dv = new_act(*x.shape, 1, torch.float32, x.device).view(x.shape)
+    _lib.check(_lib.load().mi355_medicalnet_norm_bwd(g.data_ptr(), x.data_ptr(), mean_std.data_ptr(), part.data_ptr(), part.shape[0],
+                                                     dv.data_ptr(), x.numel(), _stream()), "medicalnet_norm_bwd")
+    return dv
