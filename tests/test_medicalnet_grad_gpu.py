@@ -1,74 +1,34 @@
 """Backward of the MedicalNet Perceptual term on the GPU (csrc/medicalnet_bwd.hip) against tests/medicalnet_grad_ref.py.
 
-Bounds, restated from tests/test_medicalnet_gpu.py.  A SINGLE layer on identical bf16-exact inputs may differ from the reference only
-by the rounding of single elements (f32 summation order): rel-L2 <= 1e-3, no element further off than one bf16 spacing at the
-tensor's largest magnitude, at most 10 % of the elements different.  The WHOLE term is triangulated between the f64 reference and
-the bf16-emulating one: rel(hip, f64) <= 1.25 rel(emu, f64) + 0.02 and rel(hip, emu) <= rel(emu, f64) + 0.02.
+The bounds are those of tests/medicalnet_checks.py, shared with tests/test_medicalnet_gpu.py: single_layer_check for one layer on
+identical bf16-exact inputs; the WHOLE term is triangulated between the f64 reference and the bf16-emulating one.
 Every device call under test runs on poisoned fresh memory (tests/alloc_poison.py).  The measured figures are printed
 (pytest -s shows them) and quoted in DESIGN.md 8.13.
 """
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
 
 import medicalnet_grad_ref as GR
 import medicalnet_ref as MR
+import medicalnet_checks as C
 from alloc_poison import KINDS, poisoned
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _log(line):
-    print(line)
-
-
-def _rel(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _q16(t):
-    return t.to(torch.bfloat16).float()
-
-
-def _single_layer_check(tag, got, ref):
-    """got / ref: bf16-representable f32 tensors of one layer on identical inputs"""
-    diff = (got - ref).abs()
-    frac = float((diff > 0).float().mean())
-    worst = float(diff.max() / (ref.abs().max() * 2.0 ** -7))
-    rel = _rel(got, ref)
-    _log(f"{tag}: rel-L2 {rel:.2e}, max diff {worst:.2f} bf16 spacings at the tensor's scale, differing elements {frac:.2e}")
-    assert rel <= 1e-3, rel
-    assert worst <= 1.0, worst
-    assert frac <= 0.10, frac
-
-
-def _triangulate(tag, d_hip_f64, d_hip_emu, d_emu_f64):
-    _log(f"{tag}: rel(hip, f64) {d_hip_f64:.3e}, rel(hip, emu) {d_hip_emu:.3e}, rel(emu, f64) {d_emu_f64:.3e}")
-    assert d_hip_f64 <= 1.25 * d_emu_f64 + 0.02, (d_hip_f64, d_emu_f64)
-    assert d_hip_emu <= d_emu_f64 + 0.02, (d_hip_emu, d_emu_f64)
-
-
-def _to_ndhwc(x):
-    return x.permute(0, 2, 3, 4, 1).contiguous().to(DEV, torch.bfloat16)
-
-
-def _from_ndhwc(a):
-    return a.float().permute(0, 4, 1, 2, 3).cpu()
+DEV = C.DEV
+triangulate_f64 = functools.partial(C.triangulate, ref="f64")        # the exact reference of a gradient is f64
 
 
 @pytest.fixture(scope="module")
 def refnet():
-    return MR.random_init(MR.RefResNet10(), seed=11)
+    return C.make_refnet()
 
 
 @pytest.fixture(scope="module")
 def net(hip, refnet):
-    from unet_bssfp_amd.medicalnet import MedicalNetResNet10
-    m = MedicalNetResNet10()
-    m.load_state_dict(refnet.state_dict(), strict=True)
-    return m.to(DEV)
+    return C.make_net(refnet)
 
 
 # ------------------------------------------------------------------------------------------ data gradient, single layers
@@ -89,23 +49,23 @@ def test_dgrad_single_layer(hip, cin, cout, ks, stride, dil, add_mask):
     g = torch.Generator().manual_seed(1000 * ks + 100 * stride + dil + cin)
     x = torch.zeros(2, cin, 5, 6, 9, requires_grad=True)
     w = torch.randn(cout, cin, ks, ks, ks, generator=g) * (2.0 / (ks ** 3 * cin)) ** 0.5
-    y = F.conv3d(x, _q16(w), None, stride, dil * (ks // 2), dil)
-    dy = _q16(torch.randn(y.shape, generator=g))
+    y = F.conv3d(x, C.q16(w), None, stride, dil * (ks // 2), dil)
+    dy = C.q16(torch.randn(y.shape, generator=g))
     want, = torch.autograd.grad(y, x, dy)
     add = mask = None
     if add_mask:
-        add, mask = _q16(torch.randn(x.shape, generator=g)), _q16(torch.randn(x.shape, generator=g))
+        add, mask = C.q16(torch.randn(x.shape, generator=g)), C.q16(torch.randn(x.shape, generator=g))
         assert 0.4 < float((mask <= 0).float().mean()) < 0.6
         want = torch.where(mask > 0, want + add, torch.zeros_like(want))
-    want = _q16(want)
+    want = C.q16(want)
     wp = pack_dgrad_weight(w).to(DEV)
-    dy_d = _to_ndhwc(dy)
-    add_d, mask_d = (None, None) if add is None else (_to_ndhwc(add), _to_ndhwc(mask))
+    dy_d = C.to_ndhwc(dy)
+    add_d, mask_d = (None, None) if add is None else (C.to_ndhwc(add), C.to_ndhwc(mask))
     with poisoned("nan"):
         got = ops.medicalnet_dgrad(dy_d, wp, (2, 5, 6, 9, cin), ks, stride, dil, add=add_d, mask=mask_d)
         torch.cuda.synchronize()
     assert tuple(got.shape) == (2, 5, 6, 9, cin) and got.dtype == torch.bfloat16
-    _single_layer_check(f"dgrad {cin}->{cout} k{ks} s{stride} d{dil}" + (" +add +mask" if add_mask else ""), _from_ndhwc(got), want)
+    C.single_layer_check(f"dgrad {cin}->{cout} k{ks} s{stride} d{dil}" + (" +add +mask" if add_mask else ""), C.from_ndhwc(got), want)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -119,18 +79,18 @@ def test_dgrad_writes_zeros_where_no_tap_reaches(hip, kind):
     wp = pack_dgrad_weight(w).to(DEV)
     for ext in ((5, 6, 9), (1, 2, 3)):
         out = tuple((n - 1) // 2 + 1 for n in ext)
-        dy = _q16(torch.randn(2, 128, *out, generator=g))
-        dy_d = _to_ndhwc(dy)
+        dy = C.q16(torch.randn(2, 128, *out, generator=g))
+        dy_d = C.to_ndhwc(dy)
         with poisoned(kind):
             got = ops.medicalnet_dgrad(dy_d, wp, (2, *ext, 64), 1, 2, 1)
             torch.cuda.synchronize()
-        got = _from_ndhwc(got)
+        got = C.from_ndhwc(got)
         reached = torch.zeros(ext, dtype=torch.bool)
         reached[::2, ::2, ::2] = True
         assert bool(torch.isfinite(got).all())
         assert got[:, :, ~reached].abs().max().item() == 0.0
-        want = _q16(torch.einsum("nodhw,oc->ncdhw", dy, _q16(w).view(128, 64)))
-        _single_layer_check(f"dgrad k1 s2 {ext} ({kind})", got[:, :, ::2, ::2, ::2], want)
+        want = C.q16(torch.einsum("nodhw,oc->ncdhw", dy, C.q16(w).view(128, 64)))
+        C.single_layer_check(f"dgrad k1 s2 {ext} ({kind})", got[:, :, ::2, ::2, ::2], want)
 
 
 def test_dgrad_refuses_unsupported_shapes(hip):
@@ -189,14 +149,14 @@ def test_pool_backward_takes_the_first_maximum_of_a_tie(hip):
     a = x.clone().requires_grad_()
     pooled = F.max_pool3d(a, 3, 2, 1)
     assert _positive_ties(x, pooled.detach()) > 0.3 * pooled.numel()
-    dy = _q16(torch.randn(pooled.shape, generator=g))
+    dy = C.q16(torch.randn(pooled.shape, generator=g))
     want, = torch.autograd.grad(pooled, a, dy)
-    want = _q16(want * (x > 0))
-    x_d, dy_d = _to_ndhwc(x), _to_ndhwc(dy)
+    want = C.q16(want * (x > 0))
+    x_d, dy_d = C.to_ndhwc(x), C.to_ndhwc(dy)
     with poisoned("big"):
         got = ops.medicalnet_maxpool_bwd(x_d, dy_d)
         torch.cuda.synchronize()
-    _single_layer_check("pool backward, ties", _from_ndhwc(got), want)
+    C.single_layer_check("pool backward, ties", C.from_ndhwc(got), want)
 
 
 @pytest.mark.parametrize("case", ["offset", "border_slab"])
@@ -209,19 +169,19 @@ def test_pool_backward_with_the_stem_mask(hip, net, case):
     p = net.packed()
     xd = x.to(DEV)
     stem = ops.medicalnet_stem(xd.view(-1, *xd.shape[2:]), ops.medicalnet_moments(xd), p["stem.w"], p["stem.b"])
-    s_cpu = _from_ndhwc(stem)
+    s_cpu = C.from_ndhwc(stem)
     a = s_cpu.clone().requires_grad_()
     pooled = F.max_pool3d(a, 3, 2, 1)
-    dy = _q16(torch.randn(pooled.shape, generator=g))
+    dy = C.q16(torch.randn(pooled.shape, generator=g))
     want, = torch.autograd.grad(pooled, a, dy)
-    want = _q16(want * (s_cpu > 0))
-    _log(f"pool backward ({case}): {_positive_ties(s_cpu, pooled.detach())} windows whose positive maximum occurs more than once")
-    dy_d = _to_ndhwc(dy)
+    want = C.q16(want * (s_cpu > 0))
+    C.log(f"pool backward ({case}): {_positive_ties(s_cpu, pooled.detach())} windows whose positive maximum occurs more than once")
+    dy_d = C.to_ndhwc(dy)
     with poisoned("nan"):
         got = ops.medicalnet_maxpool_bwd(stem, dy_d)
         torch.cuda.synchronize()
     assert got.shape == stem.shape
-    _single_layer_check(f"pool backward x stem mask ({case})", _from_ndhwc(got), want)
+    C.single_layer_check(f"pool backward x stem mask ({case})", C.from_ndhwc(got), want)
 
 
 @pytest.mark.parametrize("case", ["offset", "border_slab"])
@@ -234,35 +194,35 @@ def test_stem_dgrad_and_normalisation_backward(hip, net, refnet, case):
     p = net.packed()
     w, _ = MR.fold(refnet.conv1, refnet.bn1)
     xh = torch.zeros(3, 1, 17, 20, 23, requires_grad=True)
-    y = F.conv3d(xh, _q16(w), None, 2, 3)
-    dy = _q16(torch.randn(y.shape, generator=g)) * (torch.rand(y.shape, generator=g) > 0.5)     # as behind a ReLU mask
+    y = F.conv3d(xh, C.q16(w), None, 2, 3)
+    dy = C.q16(torch.randn(y.shape, generator=g)) * (torch.rand(y.shape, generator=g) > 0.5)     # as behind a ReLU mask
     want, = torch.autograd.grad(y, xh, dy)
     xd = x.to(DEV)
     vols = xd.view(-1, *xd.shape[2:])
     ms = ops.medicalnet_moments(xd)
-    dy_d = _to_ndhwc(dy)
+    dy_d = C.to_ndhwc(dy)
     with poisoned("nan"):
         got, part = ops.medicalnet_stem_dgrad(dy_d, p["stem.dw"], vols, ms)
         dv = ops.medicalnet_norm_bwd(got, vols, ms, part)
         torch.cuda.synchronize()
     assert got.dtype == torch.float32 and got.shape == vols.shape
     got_c = got.cpu().view(want.shape)
-    rel = _rel(got_c, want)
-    _log(f"stem dgrad ({case}), f32 as it is: rel-L2 {rel:.2e}")
+    rel = C.rel(got_c, want)
+    C.log(f"stem dgrad ({case}), f32 as it is: rel-L2 {rel:.2e}")
     assert rel <= 1e-3, rel
-    _single_layer_check(f"stem dgrad ({case}), both rounded to bf16", _q16(got_c), _q16(want))
+    C.single_layer_check(f"stem dgrad ({case}), both rounded to bf16", C.q16(got_c), C.q16(want))
     mean, std = ms.cpu().double()
     x_hat = (x.double() - mean) / std
     sums = part.cpu().sum(0)
     for name, s_got, s_want in (("sum g", sums[0], got_c.double().sum()), ("sum g x^", sums[1], (got_c.double() * x_hat).sum())):
         err = abs(s_got.item() - s_want.item()) / abs(s_want.item())
-        _log(f"stem dgrad ({case}): {name} {s_got.item():.9e}, f64 sum of the device's g {s_want.item():.9e}, relative {err:.1e}")
+        C.log(f"stem dgrad ({case}): {name} {s_got.item():.9e}, f64 sum of the device's g {s_want.item():.9e}, relative {err:.1e}")
         assert err <= 1e-6, (name, err)
     # the last launch: closed form in f64 from the device's g.  f32 mean / std and f32 arithmetic on values of order |g|:
     # 1e-5 of the tensor's scale leaves two decimal digits of room over eps_f32 * (|mean| / std + a few operations)
     want_dv = GR.normalise_backward(got_c.double(), x.double())
     err = (dv.cpu().view(want_dv.shape).double() - want_dv).abs().max().item() / want_dv.abs().max().item()
-    _log(f"normalisation backward ({case}): max error {err:.1e} of the tensor's scale")
+    C.log(f"normalisation backward ({case}): max error {err:.1e} of the tensor's scale")
     assert err <= 1e-5, err
 
 
@@ -308,18 +268,18 @@ def test_perceptual_gradient_triangulated(hip, net, grad_case):
     plain = losses.PerceptualLoss(net, factor=FACTOR)(y_hat.to(DEV), y.to(DEV))
     assert torch.equal(value, plain), (value.item(), plain.item())         # the non-differentiable path's value, bit for bit
     assert torch.equal(losses.PerceptualLoss(net)(y_hat.to(DEV), y.to(DEV)) * FACTOR, plain)
-    _log(f"Perceptual value x 1e3: hip {value.item():.6e}, f64 {ref['f64'][0].item():.6e}, emu {ref['emu'][0].item():.6e}")
+    C.log(f"Perceptual value x 1e3: hip {value.item():.6e}, f64 {ref['f64'][0].item():.6e}, emu {ref['emu'][0].item():.6e}")
     got = grad.cpu()
-    _log(f"rel(f32, f64) of the gradient {_rel(ref['f32'][1], ref['f64'][1]):.3e}")
-    _triangulate("dL/dy_hat, (B, C) = (2, 2) at 33 x 40 x 47", _rel(got, ref["f64"][1]), _rel(got, ref["emu"][1]),
-                 _rel(ref["emu"][1], ref["f64"][1]))
+    C.log(f"rel(f32, f64) of the gradient {C.rel(ref['f32'][1], ref['f64'][1]):.3e}")
+    triangulate_f64("dL/dy_hat, (B, C) = (2, 2) at 33 x 40 x 47", C.rel(got, ref["f64"][1]), C.rel(got, ref["emu"][1]),
+                 C.rel(ref["emu"][1], ref["f64"][1]))
     # f32 reference: the f64 one in single precision, a third witness that the f64 bound is not met by luck
-    assert _rel(got, ref["f32"][1]) <= 1.25 * _rel(ref["emu"][1], ref["f32"][1]) + 0.02
+    assert C.rel(got, ref["f32"][1]) <= 1.25 * C.rel(ref["emu"][1], ref["f32"][1]) + 0.02
     for c in range(2):                                                    # every channel's gradient lands in its own channel
-        own = _rel(got[:, c], ref["f64"][1][:, c])
-        swapped = _rel(got[:, c], ref["f64"][1][:, 1 - c])
-        _log(f"channel {c}: rel to its own reference channel {own:.3e}, to the other {swapped:.3e}")
-        assert own <= 1.25 * _rel(ref["emu"][1][:, c], ref["f64"][1][:, c]) + 0.02 and swapped > 0.5, (c, own, swapped)
+        own = C.rel(got[:, c], ref["f64"][1][:, c])
+        swapped = C.rel(got[:, c], ref["f64"][1][:, 1 - c])
+        C.log(f"channel {c}: rel to its own reference channel {own:.3e}, to the other {swapped:.3e}")
+        assert own <= 1.25 * C.rel(ref["emu"][1][:, c], ref["f64"][1][:, c]) + 0.02 and swapped > 0.5, (c, own, swapped)
     # a second backward gives the same bits, also on memory poisoned with the other value
     again = _hip_value_and_grad(net, y_hat, y, poison="big")
     assert torch.equal(again[0], value) and torch.equal(again[1], grad)
@@ -345,15 +305,15 @@ def test_perturbing_one_target_channel_moves_the_gradient_as_in_the_reference(hi
         delta[m] = (GR.perceptual_value_and_grad(refnet, y_hat, y2, m, FACTOR)[1]
                     - GR.perceptual_value_and_grad(refnet, y_hat, y, m, FACTOR)[1])
     delta["hip"] = (_hip_value_and_grad(net, y_hat, y2)[1] - _hip_value_and_grad(net, y_hat, y)[1]).cpu()
-    _triangulate("change of dL/dy_hat", _rel(delta["hip"], delta["f64"]), _rel(delta["hip"], delta["emu"]),
-                 _rel(delta["emu"], delta["f64"]))
+    triangulate_f64("change of dL/dy_hat", C.rel(delta["hip"], delta["f64"]), C.rel(delta["hip"], delta["emu"]),
+                 C.rel(delta["emu"], delta["f64"]))
     for c in range(2):
-        own = _rel(delta["hip"][:, c], delta["f64"][:, c])
-        swapped = _rel(delta["hip"][:, c], delta["f64"][:, 1 - c])
+        own = C.rel(delta["hip"][:, c], delta["f64"][:, c])
+        swapped = C.rel(delta["hip"][:, c], delta["f64"][:, 1 - c])
         share = (delta["hip"][:, c].double().norm() / delta["hip"].double().norm()).item()
-        _log(f"change in channel {c}: share of the whole change {share:.3f}, rel to its own reference channel {own:.3e}, "
+        C.log(f"change in channel {c}: share of the whole change {share:.3f}, rel to its own reference channel {own:.3e}, "
              f"to the other {swapped:.3e}")
-        assert own <= 1.25 * _rel(delta["emu"][:, c], delta["f64"][:, c]) + 0.02 and swapped > 0.5, (c, own, swapped)
+        assert own <= 1.25 * C.rel(delta["emu"][:, c], delta["f64"][:, c]) + 0.02 and swapped > 0.5, (c, own, swapped)
 
 
 # ------------------------------------------------------------------------------------------ hipGraph
@@ -426,7 +386,7 @@ def test_generator_step_on_the_reference_objective(hip, net):
     assert grads and set(grads) == set(plain_grads)
     # a convolution bias in front of a normalisation has no gradient under any objective: exactly zero in both steps
     idle = [n for n in grads if not grads[n].any() and not plain_grads[n].any()]
-    _log(f"generator step: {len(grads)} gradients, exactly zero under both objectives: {idle}")
+    C.log(f"generator step: {len(grads)} gradients, exactly zero under both objectives: {idle}")
     assert all(n.endswith(".bias") for n in idle) and len(idle) < len(grads) // 2, idle
     for name, gr in grads.items():
         assert bool(torch.isfinite(gr).all()), name

@@ -3,7 +3,7 @@ tensor, 96 in all -- whole and by part, the achieved FLOP/s of its convolutions 
 stock torch in bf16 (channels-last Conv3d + eval BatchNorm3d modules) on the same GPU.  Device events, warm-up, interleaved
 rounds in one process; one JSON line per measurement (median and min over the rounds, ms).
 
-    python tools/bench_perceptual.py [--parts ours,stock] [--reps 10] [--batch 8] [--channels 6] [--size 64]
+    python tools/bench_perceptual.py [--parts ours,stock] [--reps 10] [--batch 8] [--channels 6] [--size 64] [--lib LIB]
 
 ``--parts backward,stock_backward`` measures the backward with respect to the prediction the same way: whole and by part (tail,
 every block's data-gradient launches, pool, stem, normalisation), a data gradient counted with its forward's FLOPs, next to the
@@ -245,7 +245,11 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--channels", type=int, default=6)
     ap.add_argument("--size", type=int, default=64)
+    ap.add_argument("--lib", default=None, help="another build of the C ABI, e.g. the parent commit's, for an interleaved A/B")
     a = ap.parse_args()
+    if a.lib:
+        import tools.diaglib as D
+        D.use(a.lib)
     assert torch.cuda.is_available(), "this tool measures on the GPU"
     g = torch.Generator().manual_seed(3)
     shape = (a.batch, a.channels, a.size, a.size, a.size)
@@ -253,7 +257,7 @@ if __name__ == "__main__":
     pred = (target + 0.2 * torch.randn(shape, generator=g)).cuda()
     target = target.cuda()
     net = random_net()
-    print(json.dumps(dict(what="shape", pred=list(shape), samples_per_tensor=a.batch * a.channels)), flush=True)
+    print(json.dumps(dict(what="shape", pred=list(shape), samples_per_tensor=a.batch * a.channels, lib=a.lib)), flush=True)
     parts = a.parts.split(",")
     ours = stock = None
     if "ours" in parts:

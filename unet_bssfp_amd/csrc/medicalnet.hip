@@ -17,37 +17,13 @@
 //             the re-reads hit in L1 / L2.  Epilogue: + bias, + residual (bf16), ReLU, bf16 store.
 //   tail    : one pass over the two feature tensors: per batch item the Perceptual partial sums and the spatial means for FID.
 // No atomics anywhere; every reduction has a fixed order, so calls are bit-identical.  No host read: mean and std travel by
-// device pointer.
-#include "common.h"
+// device pointer.  What the backward (csrc/medicalnet_bwd.hip) needs as well lives in csrc/medicalnet_common.h, once: the
+// implicit-GEMM loop of conv, the window scan of pool, pass 1 of tail, the tile decode of stem, the reductions and the host checks.
+#include "medicalnet_common.h"
 
 namespace {
 
-#define MNET_SUPPORTED(cond, ...)                     \
-  do {                                                \
-    if (!(cond)) {                                    \
-      mi355_set_error(__VA_ARGS__);                   \
-      return MI355_ERR_UNSUPPORTED;                   \
-    }                                                 \
-  } while (0)
-
 constexpr int kStemSteps = 25;                  // MFMA steps of the stem contraction: (49 + 1) (kd, kh) pairs x 8 / 16
-constexpr int kStemCout = 64;
-constexpr int kFeat = 512;                      // channels of layer4
-constexpr int kTailVox = 16;                    // voxels per workgroup of the tail pass
-
-template <typename T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// sum over the 256 threads of a workgroup in a fixed order; every thread gets it
-__device__ __forceinline__ double block_sum_256d(double v, double* red /* LDS, 4 doubles */) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // ---------------------------------------------------------------------------------------------------- moments
 __global__ __launch_bounds__(256) void mnet_moments_kernel(const float* __restrict__ x, long long n, double* __restrict__ part) {
@@ -103,9 +79,9 @@ constexpr int kStemTD = 4, kStemTH = 4, kStemTW = 16;
 constexpr int kPatchD = 2 * kStemTD + 5, kPatchH = 2 * kStemTH + 5, kPatchW = 2 * kStemTW + 6, kPatchPitch = 40;
 
 __global__ __launch_bounds__(256) void mnet_stem_kernel(const StemArgs a) {
-  __shared__ uint4 wlds[kStemSteps * kStemCout * 2];                      // [step][cout][16] bf16, 51.2 KB
+  __shared__ uint4 wlds[kStemSteps * kStemC * 2];                      // [step][cout][16] bf16, 51.2 KB
   __shared__ uint32_t patch[kPatchD * kPatchH * kPatchPitch / 2];         // bf16 pairs, 13.5 KB
-  for (int i = threadIdx.x; i < kStemSteps * kStemCout * 2; i += 256) wlds[i] = reinterpret_cast<const uint4*>(a.wp)[i];
+  for (int i = threadIdx.x; i < kStemSteps * kStemC * 2; i += 256) wlds[i] = reinterpret_cast<const uint4*>(a.wp)[i];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
   const float mean = a.ms[0], std = a.ms[1];
@@ -114,11 +90,9 @@ __global__ __launch_bounds__(256) void mnet_stem_kernel(const StemArgs a) {
   bias[0] = a.bias[r]; bias[1] = a.bias[32 + r];
   uint16_t* patch16 = reinterpret_cast<uint16_t*>(patch);
   for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-    long long t = tile;
-    const int tw = (int)(t % a.tiles_w); t /= a.tiles_w;
-    const int th = (int)(t % a.tiles_h); t /= a.tiles_h;
-    const int td = (int)(t % a.tiles_d); const long long s = t / a.tiles_d;
-    const int od0 = td * kStemTD, oh0 = th * kStemTH, ow0 = tw * kStemTW;
+    const Tile t = tile_decode(tile, a.tiles_d, a.tiles_h, a.tiles_w);
+    const long long s = t.s;
+    const int od0 = t.td * kStemTD, oh0 = t.th * kStemTH, ow0 = t.tw * kStemTW;
     const float* src = a.x + s * vol;
     __syncthreads();                                                      // the previous tile's fragments have been read
     for (int i = threadIdx.x; i < kPatchD * kPatchH * kPatchW; i += 256) {
@@ -151,7 +125,7 @@ __global__ __launch_bounds__(256) void mnet_stem_kernel(const StemArgs a) {
         fa[vt].v = make_uint4(p[0], p[1], p[2], p[3]);
       }
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) fb[ct].v = wlds[(kc * kStemCout + ct * 32 + r) * 2 + h];
+      for (int ct = 0; ct < 2; ++ct) fb[ct].v = wlds[(kc * kStemC + ct * 32 + r) * 2 + h];
 #pragma unroll
       for (int vt = 0; vt < 2; ++vt)
 #pragma unroll
@@ -165,7 +139,7 @@ __global__ __launch_bounds__(256) void mnet_stem_kernel(const StemArgs a) {
         const int row = acc_row(i, h);
         const int oh = oh0 + 2 * vt + (row >> 4), ow = ow0 + (row & 15);
         if (od < a.do_ && oh < a.ho && ow < a.wo) {
-          bf16_t* yp = a.y + ((((s * a.do_ + od) * a.ho + oh) * a.wo + ow) * kStemCout) + r;
+          bf16_t* yp = a.y + ((((s * a.do_ + od) * a.ho + oh) * a.wo + ow) * kStemC) + r;
 #pragma unroll
           for (int ct = 0; ct < 2; ++ct) Elem<bf16_t>::store(yp + ct * 32, fmaxf(acc[vt][ct][i] + bias[ct], 0.f));
         }
@@ -179,36 +153,12 @@ __global__ __launch_bounds__(256) void mnet_maxpool_kernel(const bf16_t* __restr
                                                            int d, int h, int w, int od_, int oh_, int ow_, int c) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  const int groups = c >> 3;
-  const int g = (int)(i % groups);
-  long long m = i / groups;
-  const int ow = (int)(m % ow_); m /= ow_;
-  const int oh = (int)(m % oh_); m /= oh_;
-  const int od = (int)(m % od_); const long long s = m / od_;
-  float best[8];
+  pool_scan<false>(x, i, d, h, w, od_, oh_, ow_, c, [=](long long out, const float (&best)[8]) {
+    Vec16<bf16_t> o;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) best[k] = -INFINITY;
-  for (int kd = 0; kd < 3; ++kd) {
-    const int id = 2 * od - 1 + kd;
-    if ((unsigned)id >= (unsigned)d) continue;
-    for (int kh = 0; kh < 3; ++kh) {
-      const int ih = 2 * oh - 1 + kh;
-      if ((unsigned)ih >= (unsigned)h) continue;
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int iw = 2 * ow - 1 + kw;
-        if ((unsigned)iw >= (unsigned)w) continue;
-        Vec16<bf16_t> v;
-        v.load(x + ((((s * d + id) * h + ih) * w + iw) * c + g * 8));
-#pragma unroll
-        for (int k = 0; k < 8; ++k) best[k] = fmaxf(best[k], v.f[k]);
-      }
-    }
-  }
-  Vec16<bf16_t> o;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) o.f[k] = best[k];
-  o.store(y + (i / groups) * c + g * 8);
+    for (int k = 0; k < 8; ++k) o.f[k] = best[k];
+    o.store(y + out);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------- residual convolutions
@@ -239,66 +189,35 @@ __global__ __launch_bounds__(256) void mnet_conv_kernel(const MnetConvArgs a) {
     sbase[vt] = s * a.di;
     id0[vt] = od * a.stride - a.pad; ih0[vt] = oh * a.stride - a.pad; iw0[vt] = ow * a.stride - a.pad;
   }
-  f32x16 acc[2][2];
+  // the source voxel of row 32 vt + r at tap (kd, kh, kw): input voxel (od, oh, ow) stride - pad + tap dil
+  const auto gather = [=](int vt, int kd, int kh, int kw, const bf16_t*& p) {
+    const int id = id0[vt] + kd * a.dil, ih = ih0[vt] + kh * a.dil, iw = iw0[vt] + kw * a.dil;
+    const bool in = ok[vt] && (unsigned)id < (unsigned)a.di && (unsigned)ih < (unsigned)a.hi && (unsigned)iw < (unsigned)a.wi;
+    const long long vox = in ? ((sbase[vt] + id) * a.hi + ih) * a.wi + iw : 0;       // padding reads voxel 0: in-bounds
+    p = a.x + vox * a.cin;
+    return in;
+  };
+  const auto epilogue = [=](const f32x16 (&acc)[2][2]) {
+    float bias[2];
+    bias[0] = a.bias[co_base + r]; bias[1] = a.bias[co_base + 32 + r];
 #pragma unroll
-  for (int vt = 0; vt < 2; ++vt)
+    for (int vt = 0; vt < 2; ++vt)
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
+      for (int i = 0; i < 16; ++i) {
+        const long long m = m0 + vt * 32 + acc_row(i, h);
+        if (m < a.m_total) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[vt][ct][i] = 0.f;
-  const int nchunk = a.cin >> 4, taps = a.ks * a.ks * a.ks;
-  // this lane's weight rows of chunk 0 / tap 0: [tap][chunk][cout][16]
-  const bf16_t* wlane = a.wp + ((long long)(co_base + r) * 16 + 8 * h);
-  for (int tap = 0; tap < taps; ++tap) {
-    const int kd = tap / (a.ks * a.ks), kr = tap - kd * a.ks * a.ks;
-    const int kh = kr / a.ks, kw = kr - kh * a.ks;
-    const bf16_t* pa[2]; bool in[2];
-#pragma unroll
-    for (int vt = 0; vt < 2; ++vt) {
-      const int id = id0[vt] + kd * a.dil, ih = ih0[vt] + kh * a.dil, iw = iw0[vt] + kw * a.dil;
-      in[vt] = ok[vt] && (unsigned)id < (unsigned)a.di && (unsigned)ih < (unsigned)a.hi && (unsigned)iw < (unsigned)a.wi;
-      const long long vox = in[vt] ? ((sbase[vt] + id) * a.hi + ih) * a.wi + iw : 0;
-      pa[vt] = a.x + vox * a.cin + 8 * h;
-    }
-    if (!__any(in[0] || in[1])) continue;                     // the whole wave reads padding at this tap
-    const bf16_t* pw = wlane + (long long)tap * nchunk * a.cout * 16;
-    for (int kc0 = 0; kc0 < nchunk; kc0 += 4) {               // cin is a multiple of 64: four steps' loads go out together
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int kc = kc0 + u;
-        Frag<bf16_t> fa[2], fb[2];
-#pragma unroll
-        for (int vt = 0; vt < 2; ++vt) {
-          fa[vt].load(reinterpret_cast<const char*>(pa[vt] + kc * 16));   // in-bounds also where the tap is padding (voxel 0)
-          if (!in[vt]) fa[vt].zero();
-        }
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) fb[ct].load(reinterpret_cast<const char*>(pw + ((long long)kc * a.cout + ct * 32) * 16));
-#pragma unroll
-        for (int vt = 0; vt < 2; ++vt)
-#pragma unroll
-          for (int ct = 0; ct < 2; ++ct) mma16(fa[vt], fb[ct], acc[vt][ct]);
-      }
-    }
-  }
-  float bias[2];
-  bias[0] = a.bias[co_base + r]; bias[1] = a.bias[co_base + 32 + r];
-#pragma unroll
-  for (int vt = 0; vt < 2; ++vt)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const long long m = m0 + vt * 32 + acc_row(i, h);
-      if (m < a.m_total) {
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-          const long long off = m * a.cout + co_base + ct * 32 + r;
-          float v = acc[vt][ct][i] + bias[ct];
-          if (a.res) v += Elem<bf16_t>::load(a.res + off);
-          if (a.relu) v = fmaxf(v, 0.f);
-          Elem<bf16_t>::store(a.y + off, v);
+          for (int ct = 0; ct < 2; ++ct) {
+            const long long off = m * a.cout + co_base + ct * 32 + r;
+            float v = acc[vt][ct][i] + bias[ct];
+            if (a.res) v += Elem<bf16_t>::load(a.res + off);
+            if (a.relu) v = fmaxf(v, 0.f);
+            Elem<bf16_t>::store(a.y + off, v);
+          }
         }
       }
-    }
+  };
+  gemm_wave(a.wp, a.ks, a.cin >> 4, a.cout, co_base, r, h, gather, epilogue);   // wp: [tap][cin / 16][cout][16]
 }
 
 // ---------------------------------------------------------------------------------------------------- tail
@@ -312,30 +231,7 @@ __global__ __launch_bounds__(256) void mnet_tail_kernel(const bf16_t* __restrict
   __shared__ double dred[4];
   const int b = blockIdx.y, chunk = blockIdx.x, v0 = chunk * kTailVox;
   const int nvec = c * (kFeat / 8);                                       // 16-byte vectors per voxel
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // pass 1: sum of squares over the channels, per voxel and tensor
-  float sq[2 * kTailVox];
-#pragma unroll
-  for (int i = 0; i < 2 * kTailVox; ++i) sq[i] = 0.f;
-  for (int ev = threadIdx.x; ev < nvec; ev += 256) {
-    const long long base = ((long long)(b * c + ev / (kFeat / 8)) * vox) * kFeat + (ev % (kFeat / 8)) * 8;
-#pragma unroll
-    for (int vi = 0; vi < kTailVox; ++vi) {
-      if (v0 + vi < vox) {
-        Vec16<bf16_t> p, t;
-        p.load(fp + base + (long long)(v0 + vi) * kFeat);
-        t.load(ft + base + (long long)(v0 + vi) * kFeat);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { sq[2 * vi] += p.f[k] * p.f[k]; sq[2 * vi + 1] += t.f[k] * t.f[k]; }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2 * kTailVox; ++i) {
-    const float s = wave_sum(sq[i]);
-    if (lane == 0) red[wave][i] = s;
-  }
-  __syncthreads();
+  tail_sums<2>(fp, ft, b, c, vox, v0, red);                               // pass 1: p . p and t . t per voxel
   if (threadIdx.x < 2 * kTailVox) {
     const int i = threadIdx.x;
     norm[i] = sqrtf((red[0][i] + red[1][i]) + (red[2][i] + red[3][i])) + 1e-10f;
@@ -344,7 +240,7 @@ __global__ __launch_bounds__(256) void mnet_tail_kernel(const bf16_t* __restrict
   // pass 2: channel sums over the chunk's voxels, and sum (p / |p| - t / |t|)^2
   float acc = 0.f;
   for (int ev = threadIdx.x; ev < nvec; ev += 256) {
-    const long long base = ((long long)(b * c + ev / (kFeat / 8)) * vox) * kFeat + (ev % (kFeat / 8)) * 8;
+    const long long base = tail_base(b, c, ev, vox);
     Vec16<bf16_t> sp, st;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { sp.f[k] = 0.f; st.f[k] = 0.f; }
@@ -409,8 +305,6 @@ int moments_blocks(long long n) {
   const long long b = (n + 256 * 32 - 1) / (256 * 32);
   return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
 }
-int out_extent(int in, int ks, int stride, int dil) { return (in + 2 * (dil * (ks / 2)) - dil * (ks - 1) - 1) / stride + 1; }
-bool is_width(int c) { return c == 64 || c == 128 || c == 256 || c == 512; }
 
 }  // namespace
 
@@ -461,14 +355,8 @@ extern "C" int mi355_medicalnet_conv(const void* x, const void* wp, const float*
                                      int32_t samples, int32_t d, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t ks,
                                      int32_t stride, int32_t dilation, int32_t relu, void* stream) {
   MI355_REQUIRE(x && wp && bias && y, "medicalnet_conv: null pointer");
-  MI355_REQUIRE(samples > 0 && d > 0 && h > 0 && w > 0, "medicalnet_conv: bad shape (samples=%d d=%d h=%d w=%d)", samples, d, h, w);
-  MNET_SUPPORTED(is_width(cin) && is_width(cout), "medicalnet_conv: cin and cout must be 64, 128, 256 or 512 (cin=%d cout=%d)",
-                 cin, cout);
-  MNET_SUPPORTED((ks == 3 && (dilation == 1 || dilation == 2 || dilation == 4)) || (ks == 1 && dilation == 1),
-                 "medicalnet_conv: ks 3 with dilation 1, 2 or 4, or ks 1 with dilation 1 (ks=%d dilation=%d)", ks, dilation);
-  MNET_SUPPORTED(stride == 1 || stride == 2, "medicalnet_conv: stride must be 1 or 2 (stride=%d)", stride);
-  MI355_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wp)) & 15) == 0,
-                "medicalnet_conv: x and the packed weights must be 16-byte aligned");
+  const int rc = check_conv_args("medicalnet_conv", "x", x, wp, samples, d, h, w, cin, cout, ks, stride, dilation);
+  if (rc != MI355_OK) return rc;
   MnetConvArgs a;
   a.x = (const bf16_t*)x; a.wp = (const bf16_t*)wp; a.bias = bias; a.res = (const bf16_t*)residual; a.y = (bf16_t*)y;
   a.di = d; a.hi = h; a.wi = w;

@@ -19,39 +19,13 @@
 //                 for the normalisation backward.
 //   norm_bwd    : dv = (g - sum g / N - x^ sum(g x^) / (N - 1)) / std, the gradient through (v - mean) / std (unbiased).
 // No atomics; every reduction has a fixed order, so two calls give identical bits.  No host read.
-#include "common.h"
+// Shared with the forward through csrc/medicalnet_common.h, one definition each: the implicit-GEMM loop (dgrad = conv with another
+// gather and epilogue), the pool window scan (arg-max = the forward's scan keeping the tap), pass 1 of the tail, the tile decode.
+#include "medicalnet_common.h"
 
 namespace {
 
-#define MNET_SUPPORTED(cond, ...)                     \
-  do {                                                \
-    if (!(cond)) {                                    \
-      mi355_set_error(__VA_ARGS__);                   \
-      return MI355_ERR_UNSUPPORTED;                   \
-    }                                                 \
-  } while (0)
-
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-constexpr int kFeat = 512;                      // channels of layer4
-constexpr int kTailVox = 16;                    // voxels per workgroup of the tail pass
-constexpr int kStemC = 64;
-
-template <typename T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double block_sum_256d(double v, double* red /* LDS, 4 doubles */) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-int out_extent(int in, int ks, int stride, int dil) { return (in + 2 * (dil * (ks / 2)) - dil * (ks - 1) - 1) / stride + 1; }
-bool is_width(int c) { return c == 64 || c == 128 || c == 256 || c == 512; }
 
 // ---------------------------------------------------------------------------------------------------- tail backward
 // grid (chunks, items), as mnet_tail_kernel.  With n = |f|, a = n + 1e-10 and s = 2 g_out / (items * vox):
@@ -64,31 +38,7 @@ __global__ __launch_bounds__(256) void mnet_tail_bwd_kernel(const bf16_t* __rest
   __shared__ float coef[2 * kTailVox];
   const int b = blockIdx.y, v0 = blockIdx.x * kTailVox;
   const int nvec = c * (kFeat / 8);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float sq[3 * kTailVox];
-#pragma unroll
-  for (int i = 0; i < 3 * kTailVox; ++i) sq[i] = 0.f;
-  for (int ev = threadIdx.x; ev < nvec; ev += 256) {
-    const long long base = ((long long)(b * c + ev / (kFeat / 8)) * vox) * kFeat + (ev % (kFeat / 8)) * 8;
-#pragma unroll
-    for (int vi = 0; vi < kTailVox; ++vi) {
-      if (v0 + vi < vox) {
-        Vec16<bf16_t> p, t;
-        p.load(fp + base + (long long)(v0 + vi) * kFeat);
-        t.load(ft + base + (long long)(v0 + vi) * kFeat);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          sq[3 * vi] += p.f[k] * p.f[k]; sq[3 * vi + 1] += t.f[k] * t.f[k]; sq[3 * vi + 2] += p.f[k] * t.f[k];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 3 * kTailVox; ++i) {
-    const float s = wave_sum(sq[i]);
-    if (lane == 0) red[wave][i] = s;
-  }
-  __syncthreads();
+  tail_sums<3>(fp, ft, b, c, vox, v0, red);                               // p . p, t . t and p . t per voxel
   if (threadIdx.x < kTailVox) {
     const int vi = threadIdx.x;
     float tot[3];
@@ -106,7 +56,7 @@ __global__ __launch_bounds__(256) void mnet_tail_bwd_kernel(const bf16_t* __rest
   }
   __syncthreads();
   for (int ev = threadIdx.x; ev < nvec; ev += 256) {
-    const long long base = ((long long)(b * c + ev / (kFeat / 8)) * vox) * kFeat + (ev % (kFeat / 8)) * 8;
+    const long long base = tail_base(b, c, ev, vox);
 #pragma unroll
     for (int vi = 0; vi < kTailVox; ++vi) {
       if (v0 + vi < vox) {
@@ -143,7 +93,7 @@ __global__ __launch_bounds__(256) void mnet_dgrad_kernel(const MnetDgradArgs a) 
   for (int k = 1; k < a.ncls; ++k) cls += wid >= a.wave0[k] ? 1 : 0;
   const int step = a.stride;
   const int pd = step == 2 ? (cls >> 2) & 1 : 0, ph = step == 2 ? (cls >> 1) & 1 : 0, pw = step == 2 ? cls & 1 : 0;
-  const int nd = (a.di - pd + step - 1) / step, nh = (a.hi - ph + step - 1) / step, nw = (a.wi - pw + step - 1) / step;
+  const int nd = class_extent(a.di, pd, step), nh = class_extent(a.hi, ph, step), nw = class_extent(a.wi, pw, step);
   const long long per = (long long)nd * nh * nw, count = per * a.samples;
   const int ci_base = blockIdx.y * 64;
   int s_[2], id_[2], ih_[2], iw_[2], vox[2];                    // vox: linear input voxel of this lane's row, -1 = none
@@ -158,65 +108,35 @@ __global__ __launch_bounds__(256) void mnet_dgrad_kernel(const MnetDgradArgs a) 
     s_[vt] = s; id_[vt] = jd * step + pd; ih_[vt] = jh * step + ph; iw_[vt] = jw * step + pw;
     vox[vt] = ok ? ((s * a.di + id_[vt]) * a.hi + ih_[vt]) * a.wi + iw_[vt] : -1;
   }
-  f32x16 acc[2][2];
+  const int sh = step - 1;
+  // the source voxel of row 32 vt + r at tap (kd, kh, kw): dy at (i + pad - tap dil) / stride, where that is exact and in range
+  const auto gather = [=](int vt, int kd, int kh, int kw, const bf16_t*& p) {
+    const int qd = id_[vt] + a.pad - kd * a.dil, qh = ih_[vt] + a.pad - kh * a.dil, qw = iw_[vt] + a.pad - kw * a.dil;
+    const int od = qd >> sh, oh = qh >> sh, ow = qw >> sh;
+    const bool in = vox[vt] >= 0 && qd >= 0 && qh >= 0 && qw >= 0 && ((qd | qh | qw) & sh) == 0 && od < a.do_ && oh < a.ho && ow < a.wo;
+    const long long o = in ? (((long long)s_[vt] * a.do_ + od) * a.ho + oh) * a.wo + ow : 0;     // a dead tap reads voxel 0: in-bounds
+    p = a.dy + o * a.cout;
+    return in;
+  };
+  const auto epilogue = [=](const f32x16 (&acc)[2][2]) {
 #pragma unroll
-  for (int vt = 0; vt < 2; ++vt)
+    for (int vt = 0; vt < 2; ++vt)
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
+      for (int i = 0; i < 16; ++i) {
+        const int v = __shfl(vox[vt], acc_row(i, h), 64);       // lane `row` (h = 0) holds the voxel of accumulator row `row`
+        if (v >= 0) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[vt][ct][i] = 0.f;
-  const int nchunk = a.cout >> 4, taps = a.ks * a.ks * a.ks, sh = step - 1;
-  // this lane's weight rows of chunk 0 / tap 0: [tap][chunk][cin][16]
-  const bf16_t* wlane = a.wp + ((long long)(ci_base + r) * 16 + 8 * h);
-  for (int tap = 0; tap < taps; ++tap) {
-    const int kd = tap / (a.ks * a.ks), kr = tap - kd * a.ks * a.ks;
-    const int kh = kr / a.ks, kw = kr - kh * a.ks;
-    const bf16_t* pa[2]; bool in[2];
-#pragma unroll
-    for (int vt = 0; vt < 2; ++vt) {
-      const int qd = id_[vt] + a.pad - kd * a.dil, qh = ih_[vt] + a.pad - kh * a.dil, qw = iw_[vt] + a.pad - kw * a.dil;
-      const int od = qd >> sh, oh = qh >> sh, ow = qw >> sh;
-      in[vt] = vox[vt] >= 0 && qd >= 0 && qh >= 0 && qw >= 0 && ((qd | qh | qw) & sh) == 0 && od < a.do_ && oh < a.ho && ow < a.wo;
-      const long long o = in[vt] ? (((long long)s_[vt] * a.do_ + od) * a.ho + oh) * a.wo + ow : 0;
-      pa[vt] = a.dy + o * a.cout + 8 * h;
-    }
-    if (!__any(in[0] || in[1])) continue;                     // no voxel of the wave is reached by this tap
-    const bf16_t* pw_ = wlane + (long long)tap * nchunk * a.cin * 16;
-    for (int kc0 = 0; kc0 < nchunk; kc0 += 4) {               // cout is a multiple of 64: four steps' loads go out together
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int kc = kc0 + u;
-        Frag<bf16_t> fa[2], fb[2];
-#pragma unroll
-        for (int vt = 0; vt < 2; ++vt) {
-          fa[vt].load(reinterpret_cast<const char*>(pa[vt] + kc * 16));   // in-bounds also where the tap is dead (voxel 0)
-          if (!in[vt]) fa[vt].zero();
-        }
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) fb[ct].load(reinterpret_cast<const char*>(pw_ + ((long long)kc * a.cin + ct * 32) * 16));
-#pragma unroll
-        for (int vt = 0; vt < 2; ++vt)
-#pragma unroll
-          for (int ct = 0; ct < 2; ++ct) mma16(fa[vt], fb[ct], acc[vt][ct]);
-      }
-    }
-  }
-#pragma unroll
-  for (int vt = 0; vt < 2; ++vt)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int v = __shfl(vox[vt], acc_row(i, h), 64);       // lane `row` (h = 0) holds the voxel of accumulator row `row`
-      if (v >= 0) {
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-          const long long off = (long long)v * a.cin + ci_base + ct * 32 + r;
-          float g = acc[vt][ct][i];
-          if (a.add) g += Elem<bf16_t>::load(a.add + off);
-          if (a.mask && !(Elem<bf16_t>::load(a.mask + off) > 0.f)) g = 0.f;
-          Elem<bf16_t>::store(a.dx + off, g);
+          for (int ct = 0; ct < 2; ++ct) {
+            const long long off = (long long)v * a.cin + ci_base + ct * 32 + r;
+            float g = acc[vt][ct][i];
+            if (a.add) g += Elem<bf16_t>::load(a.add + off);
+            if (a.mask && !(Elem<bf16_t>::load(a.mask + off) > 0.f)) g = 0.f;
+            Elem<bf16_t>::store(a.dx + off, g);
+          }
         }
       }
-    }
+  };
+  gemm_wave(a.wp, a.ks, a.cout >> 4, a.cin, ci_base, r, h, gather, epilogue);   // wp: [tap][cout / 16][cin][16]
 }
 
 // ---------------------------------------------------------------------------------------------------- max-pool backward
@@ -225,36 +145,11 @@ __global__ __launch_bounds__(256) void mnet_pool_argmax_kernel(const bf16_t* __r
                                                                int d, int h, int w, int od_, int oh_, int ow_, int c) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  const int groups = c >> 3;
-  const int g = (int)(i % groups);
-  long long m = i / groups;
-  const int ow = (int)(m % ow_); m /= ow_;
-  const int oh = (int)(m % oh_); m /= oh_;
-  const int od = (int)(m % od_); const long long s = m / od_;
-  float best[8]; uint32_t idx[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { best[k] = -INFINITY; idx[k] = 13; }   // the centre tap is always in range
-  for (int kd = 0; kd < 3; ++kd) {
-    const int id = 2 * od - 1 + kd;
-    if ((unsigned)id >= (unsigned)d) continue;
-    for (int kh = 0; kh < 3; ++kh) {
-      const int ih = 2 * oh - 1 + kh;
-      if ((unsigned)ih >= (unsigned)h) continue;
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int iw = 2 * ow - 1 + kw;
-        if ((unsigned)iw >= (unsigned)w) continue;
-        Vec16<bf16_t> v;
-        v.load(x + ((((s * d + id) * h + ih) * w + iw) * c + g * 8));
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-          if (v.f[k] > best[k]) { best[k] = v.f[k]; idx[k] = kd * 9 + kh * 3 + kw; }
-      }
-    }
-  }
-  const uint32_t lo = idx[0] | (idx[1] << 8) | (idx[2] << 16) | (idx[3] << 24);
-  const uint32_t hi = idx[4] | (idx[5] << 8) | (idx[6] << 16) | (idx[7] << 24);
-  *reinterpret_cast<uint2*>(arg + (i / groups) * c + g * 8) = make_uint2(lo, hi);
+  pool_scan<true>(x, i, d, h, w, od_, oh_, ow_, c, [=](long long out, const uint32_t (&idx)[8]) {
+    const uint32_t lo = idx[0] | (idx[1] << 8) | (idx[2] << 16) | (idx[3] << 24);
+    const uint32_t hi = idx[4] | (idx[5] << 8) | (idx[6] << 16) | (idx[7] << 24);
+    *reinterpret_cast<uint2*>(arg + out) = make_uint2(lo, hi);
+  });
 }
 
 // one thread per (input voxel, 8 channels): dx = [x > 0] sum over the windows whose arg-max this voxel is of dy
@@ -331,17 +226,15 @@ constexpr int kSdStageVecs = (kSdPatchVecs + 255) / 256;                  // 16-
 
 // the loads of one stage (a tile's patch, one half of the channels) into registers: they fly while the previous stage computes
 __device__ __forceinline__ void sd_stage_issue(const StemDgradArgs& a, long long tile, int half, uint4 (&v)[kSdStageVecs]) {
-  long long t_ = tile;
-  const int tw = (int)(t_ % a.tiles_w); t_ /= a.tiles_w;
-  const int th = (int)(t_ % a.tiles_h); t_ /= a.tiles_h;
-  const int td = (int)(t_ % a.tiles_d); const long long s = t_ / a.tiles_d;
+  const Tile t = tile_decode(tile, a.tiles_d, a.tiles_h, a.tiles_w);
+  const long long s = t.s;
 #pragma unroll
   for (int k = 0; k < kSdStageVecs; ++k) {
     const int i = threadIdx.x + k * 256;
     const int vox = (i < kSdPatchVecs ? i : 0) >> 2, ch = i & 3;
     const int pz = vox / (kSdPH * kSdPW), r2 = vox - pz * (kSdPH * kSdPW);
     const int py = r2 / kSdPW, px = r2 - py * kSdPW;
-    const int od = td * kSdTD - 1 + pz, oh = th * kSdTH - 1 + py, ow = tw * kSdTW - 1 + px;
+    const int od = t.td * kSdTD - 1 + pz, oh = t.th * kSdTH - 1 + py, ow = t.tw * kSdTW - 1 + px;
     const bool in = (unsigned)od < (unsigned)a.do_ && (unsigned)oh < (unsigned)a.ho && (unsigned)ow < (unsigned)a.wo;
     const long long o = in ? ((s * a.do_ + od) * a.ho + oh) * a.wo + ow : 0;
     const uint4 val = *reinterpret_cast<const uint4*>(a.dy + o * kStemC + half * 32 + ch * 8);       // in-bounds either way
@@ -361,11 +254,9 @@ __global__ __launch_bounds__(256) void mnet_stem_dgrad_kernel(const StemDgradArg
   uint4 stage[kSdStageVecs];
   sd_stage_issue(a, blockIdx.x, 0, stage);                                // (the grid never exceeds the number of tiles)
   for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-    long long t_ = tile;
-    const int tw = (int)(t_ % a.tiles_w); t_ /= a.tiles_w;
-    const int th = (int)(t_ % a.tiles_h); t_ /= a.tiles_h;
-    const int td = (int)(t_ % a.tiles_d); const long long s = t_ / a.tiles_d;
-    const int od0 = td * kSdTD, oh0 = th * kSdTH, ow0 = tw * kSdTW;
+    const Tile tl = tile_decode(tile, a.tiles_d, a.tiles_h, a.tiles_w);
+    const long long s = tl.s;
+    const int od0 = tl.td * kSdTD, oh0 = tl.th * kSdTH, ow0 = tl.tw * kSdTW;
     f32x4v acc[4];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -457,14 +348,8 @@ extern "C" int mi355_medicalnet_dgrad(const void* dy, const void* wp, const void
                                       int32_t samples, int32_t d, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t ks,
                                       int32_t stride, int32_t dilation, void* stream) {
   MI355_REQUIRE(dy && wp && dx, "medicalnet_dgrad: null pointer");
-  MI355_REQUIRE(samples > 0 && d > 0 && h > 0 && w > 0, "medicalnet_dgrad: bad shape (samples=%d d=%d h=%d w=%d)", samples, d, h, w);
-  MNET_SUPPORTED(is_width(cin) && is_width(cout), "medicalnet_dgrad: cin and cout must be 64, 128, 256 or 512 (cin=%d cout=%d)",
-                 cin, cout);
-  MNET_SUPPORTED((ks == 3 && (dilation == 1 || dilation == 2 || dilation == 4)) || (ks == 1 && dilation == 1),
-                 "medicalnet_dgrad: ks 3 with dilation 1, 2 or 4, or ks 1 with dilation 1 (ks=%d dilation=%d)", ks, dilation);
-  MNET_SUPPORTED(stride == 1 || stride == 2, "medicalnet_dgrad: stride must be 1 or 2 (stride=%d)", stride);
-  MI355_REQUIRE(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(wp)) & 15) == 0,
-                "medicalnet_dgrad: dy and the packed weights must be 16-byte aligned");
+  const int rc = check_conv_args("medicalnet_dgrad", "dy", dy, wp, samples, d, h, w, cin, cout, ks, stride, dilation);
+  if (rc != MI355_OK) return rc;
   MNET_SUPPORTED((long long)samples * d * h * w < (1ll << 31), "medicalnet_dgrad: tensor too large for one launch");
   MnetDgradArgs a;
   a.dy = (const bf16_t*)dy; a.wp = (const bf16_t*)wp; a.add = (const bf16_t*)add; a.mask = (const bf16_t*)mask; a.dx = (bf16_t*)dx;
@@ -476,8 +361,7 @@ extern "C" int mi355_medicalnet_dgrad(const void* dy, const void* wp, const void
   for (int c = 0; c < 9; ++c) a.wave0[c] = 0;
   for (int c = 0; c < a.ncls; ++c) {
     const int pd = stride == 2 ? (c >> 2) & 1 : 0, ph = stride == 2 ? (c >> 1) & 1 : 0, pw = stride == 2 ? c & 1 : 0;
-    const long long count = (long long)samples * ((d - pd + stride - 1) / stride) * ((h - ph + stride - 1) / stride) *
-                            ((w - pw + stride - 1) / stride);
+    const long long count = (long long)samples * class_extent(d, pd, stride) * class_extent(h, ph, stride) * class_extent(w, pw, stride);
     a.wave0[c] = (int)waves;
     waves += (count + 63) / 64;
   }
