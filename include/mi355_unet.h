@@ -105,8 +105,11 @@ typedef struct mi355_wpack_desc {
   const float* q_amax;
 } mi355_wpack_desc;
 int mi355_weight_pack(const mi355_wpack_desc* d, void* stream);
-/* n packings in ceil(n/16) launches (descriptors travel by value; all must share one dtype) */
+/* n packings, 16 per launch (descriptors travel by value; all must share one dtype).  A forward and a data-gradient packing of
+ * one tensor (dense 3x3x3, or space-to-depth k4 with one s2d_cp), anywhere in the list, are written from one read of the tensor. */
 int mi355_weight_pack_multi(const mi355_wpack_desc* descs, int32_t n, void* stream);
+/* host only: the number of such pairs mi355_weight_pack_multi finds in the list (< 0: an invalid descriptor) */
+int32_t mi355_weight_pack_multi_pairs(const mi355_wpack_desc* descs, int32_t n);
 
 /* ------------------------------------------------------------------------------------------
  * Implicit-GEMM 3D convolution on MFMA (forward of Conv3d; data-gradient of Conv3d and
