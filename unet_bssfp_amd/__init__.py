@@ -9,14 +9,15 @@ from .nn import (BasicUNet, Conv3d, ConvTranspose3d, Discriminator, DownSampleCo
                  compute_dtype_from_name, set_compute_dtype, set_default_compute_dtype)
 from .functional import l1_loss  # noqa: F401
 from .trainer import EarlyStopping, EpochStats, ModelCheckpoint, Trainer  # noqa: F401
+from .stages import TrainingState  # noqa: F401
 
 __all__ = ["BasicUNet", "Conv3d", "ConvTranspose3d", "Discriminator", "DownSampleConv", "Generator",
            "compute_dtype_from_name", "set_compute_dtype", "set_default_compute_dtype", "l1_loss",
-           "EarlyStopping", "EpochStats", "ModelCheckpoint", "Trainer", "train_model"]
+           "EarlyStopping", "EpochStats", "ModelCheckpoint", "Trainer", "TrainingState", "train_model", "train_staged"]
 
 
 def __getattr__(name):
-    if name == "train_model":            # lazily: ``python -m unet_bssfp_amd.train`` must not find its module imported already
-        from .train import train_model
-        return train_model
+    if name in ("train_model", "train_staged"):   # lazily: ``python -m unet_bssfp_amd.train`` must not find its module imported already
+        from . import train
+        return getattr(train, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

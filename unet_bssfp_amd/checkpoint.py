@@ -11,7 +11,9 @@ The reference trains under ``pl.Trainer`` with ``ModelCheckpoint`` (src/train.py
                         ``medicalnet.MedicalNetResNet10``
     'optimizer_states'  [gen AdamW state_dict, discr AdamW state_dict]   (configure_optimizers order, :359-361)
     'hyper_parameters'  what ``save_hyperparameters`` recorded (src/model.py:149): input_modality, lr,
-                        batch_size, perceptual_factor, recon_factor
+                        batch_size, perceptual_factor, recon_factor; a model in a training state (stages.py) adds
+                        'training_state' (a plain string, ``'TrainingState.TRANSFER'``) and 'stage_lr' -- absent without
+                        a state, so such files are what they were
     'epoch', 'global_step', 'pytorch-lightning_version', 'lr_schedulers', 'callbacks', 'loops'
 
 Files are read with ``torch.load(weights_only=True)`` only: nothing in the file is executed, and a
@@ -49,12 +51,16 @@ def checkpoint_dict(model, epoch: int = 0, global_step: int = 0) -> Dict:
         from .functional import DropoutState
         dev = next(model.gen.parameters()).device
         extra["dropout_base"] = int(DropoutState.base(dev).item())
+    hparams = {k: getattr(model, k) for k in HPARAM_KEYS}
+    if getattr(model, "training_state", None) is not None:
+        hparams["training_state"] = str(model.training_state)
+        hparams["stage_lr"] = float(model.stage_lr)
     return {
         "epoch": int(epoch), "global_step": int(global_step), "pytorch-lightning_version": LIGHTNING_VERSION,
         "state_dict": _plain({k: v for k, v in model.state_dict().items() if k.startswith(_OWN_PREFIXES)}),
         "optimizer_states": [_plain(o.state_dict()) for o in opts],
         "lr_schedulers": [], "callbacks": {}, "loops": {},
-        "hyper_parameters": {k: getattr(model, k) for k in HPARAM_KEYS},
+        "hyper_parameters": hparams,
         "mi355": extra,
     }
 
@@ -87,6 +93,13 @@ def apply_checkpoint(model, ckpt: Dict, strict: bool = True, load_optimizers: bo
         repack_weights(model.gen), repack_weights(model.discr)
     if load_optimizers and ckpt.get("optimizer_states"):
         states = ckpt["optimizer_states"]
+        # the optimisers of a training state (stages.py) cover that state's trainable parameters only
+        stored = (ckpt.get("hyper_parameters") or {}).get("training_state")
+        state = getattr(model, "training_state", None)
+        if stored != (None if state is None else str(state)):
+            raise RuntimeError(f"{path}: the checkpoint's optimiser state is that of training state {stored}, the model is in "
+                               f"{state}; call model.change_training_state(...) first, or load the weights only "
+                               "(load_optimizers=False, or load_from_checkpoint(path, training_state=...))")
         opts = model.optimizers()
         if len(states) != len(opts):
             raise RuntimeError(f"checkpoint has {len(states)} optimizer states, the model has {len(opts)} optimizers")
@@ -119,15 +132,26 @@ def medicalnet_state_dict(ckpt_or_path) -> Dict[str, torch.Tensor]:
 
 def load_from_checkpoint(path: str, device: Optional[str] = None, **overrides):
     """``bSSFPToDWITensorModel.load_from_checkpoint`` (src/train.py:57): rebuild the model from the stored
-    hyper-parameters, then load weights and both optimizer states."""
+    hyper-parameters, then load weights and both optimizer states.  A stored training state (stages.py) is restored with
+    its rate.  ``training_state=`` (a ``TrainingState``, its name, or ``None``) and ``input_modality=`` rebuild the model for
+    the next stage instead: the weights are loaded, the state's rate is the table's unless ``stage_lr=`` is given, and the
+    optimisers start fresh whenever the state, or the modality inside a state, differs from the stored one."""
     from .gan import bSSFPToDWITensorModel
-    hp = dict(torch.load(path, map_location="cpu", weights_only=True).get("hyper_parameters") or {})
-    hp = {k: v for k, v in hp.items() if k in HPARAM_KEYS}
+    from .stages import parse_state
+    stored = dict(torch.load(path, map_location="cpu", weights_only=True).get("hyper_parameters") or {})
+    hp = {k: v for k, v in stored.items() if k in HPARAM_KEYS}
+    stored_state = parse_state(stored.get("training_state"))
+    state = parse_state(overrides.pop("training_state")) if "training_state" in overrides else stored_state
+    same_stage = state is stored_state and overrides.get("input_modality", hp.get("input_modality")) == hp.get("input_modality")
+    lr = overrides.pop("stage_lr", stored.get("stage_lr") if same_stage else None)
     hp.update(overrides)
     if "input_modality" not in hp:
         raise KeyError(f"{path}: no 'input_modality' among the hyper-parameters; pass it explicitly")
     model = bSSFPToDWITensorModel(**hp)
     if device is not None:
         model = model.to(device)
-    info = load_checkpoint(model, path)
+    if state is not None:
+        model.change_training_state(state, hp["input_modality"], lr=lr)
+    # (without a state an ``input_modality=`` override keeps the optimiser state, as it always did)
+    info = load_checkpoint(model, path, load_optimizers=same_stage or (state is None and stored_state is None))
     return model, info

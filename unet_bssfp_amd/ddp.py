@@ -40,6 +40,7 @@ class _Bucket:
 class GradSync:
     def __init__(self, params: Iterable[torch.nn.Parameter], bucket_mb: float = 25.0, group=None):
         self.group = group
+        self.bucket_mb = bucket_mb
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         plist = [p for p in params]
         # de-duplicate (ModuleDicts share modules) while keeping order
@@ -168,8 +169,9 @@ def attach(model, bucket_mb: float = 25.0, group=None, broadcast: bool = True):
         # HIP networks: the gradient kernels write into flat per-stage buckets (gradsink.py); a bucket is all-reduced the
         # moment its last gradient kernel has been enqueued, under the rest of the backward pass
         return model
-    model.grad_sync_gen = GradSync(used_parameters(model.gen, modality), bucket_mb, group)
-    model.grad_sync_discr = GradSync(used_parameters(model.discr, modality), bucket_mb, group)
+    frozen = getattr(model, "_frozen", ())          # a training state (stages.py): nothing is exchanged for frozen parameters
+    model.grad_sync_gen = GradSync(used_parameters(model.gen, modality, frozen), bucket_mb, group)
+    model.grad_sync_discr = GradSync(used_parameters(model.discr, modality, frozen), bucket_mb, group)
     return model
 
 
@@ -227,11 +229,12 @@ def broadcast_buffers(model, every: int = 1, step: int = 0, group=None):
         broadcast_module_state(model.discr, 0, group, buffers_only=True)
 
 
-def used_parameters(net: torch.nn.Module, modality) -> List[torch.nn.Parameter]:
+def used_parameters(net: torch.nn.Module, modality, frozen=()) -> List[torch.nn.Parameter]:
     """Parameters that receive gradients for ``modality``: the modality heads not selected
     (src/model.py:29-34, 74-78) are excluded statically instead of DDP's dynamic
-    ``find_unused_parameters`` (src/train.py:30)."""
-    unused = set()
+    ``find_unused_parameters`` (src/train.py:30).  ``frozen``: id() of the parameters a training state keeps
+    fixed (stages.py); they receive no gradient either."""
+    unused = set(frozen)
     table = getattr(net, "blocks", None)
     if isinstance(table, torch.nn.ModuleDict) and modality in table:
         head = table[modality]

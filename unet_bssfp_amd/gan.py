@@ -45,7 +45,7 @@ class bSSFPToDWITensorModel(nn.Module):
                  gen: Optional[nn.Module] = None, discr: Optional[nn.Module] = None,
                  l1_fn: Optional[Callable] = None, optimizer_class=None,
                  extra_recon_terms: Optional[Dict[str, Callable]] = None, recon_divisor: Optional[int] = None,
-                 reference_quirks: bool = False, medicalnet: Optional[nn.Module] = None):
+                 reference_quirks: bool = False, medicalnet: Optional[nn.Module] = None, fine_tune_lr: float = 1e-5):
         super().__init__()
         self.input_modality = input_modality
         if gen is None or discr is None:
@@ -74,7 +74,14 @@ class bSSFPToDWITensorModel(nn.Module):
         self.sinks_gen = None          # gradsink.GradBuckets of the HIP networks (created at the first training step)
         self.sinks_discr = None
         self.use_grad_sinks = True
+        self._sink_cfg = None          # (group, distributed, force_collectives) the sinks were created with
         self._stage = None
+        # staged training (stages.py): None = the plain step.  Set by change_training_state() only.
+        self.training_state = None
+        self.fine_tune_lr = fine_tune_lr
+        self.stage_lr = None           # learning rate of the state (None: self.lr)
+        self.stage_version = 0         # bumped by every change_training_state(): a captured step is tied to it
+        self._frozen = frozenset()     # id() of the parameters the state keeps fixed
         self._optimizers = None
         self.last_logs: Dict[str, torch.Tensor] = {}
 
@@ -87,7 +94,75 @@ class bSSFPToDWITensorModel(nn.Module):
         if cls is None:
             from .optim import FusedAdamW
             cls = FusedAdamW if next(self.gen.parameters()).is_cuda else torch.optim.AdamW
-        return cls(self.gen.parameters(), lr=self.lr), cls(self.discr.parameters(), lr=self.lr)
+        if self.training_state is None:
+            return cls(self.gen.parameters(), lr=self.lr), cls(self.discr.parameters(), lr=self.lr)
+        # a training state: over the trainable parameters only, at the state's rate.  The frozen SET decides, not the
+        # requires_grad flags of the moment: the first call may come from inside a phase, while the other network is toggled off.
+        lr = self.lr if self.stage_lr is None else self.stage_lr
+        return cls(self.trainable(self.gen.parameters()), lr=lr), cls(self.trainable(self.discr.parameters()), lr=lr)
+
+    # ------------------------------------------------------------------ staged training (stages.py)
+    def trainable(self, params):
+        """``params`` without the parameters the training state keeps fixed (state ``None``: all of them)"""
+        return [p for p in params if id(p) not in self._frozen]
+
+    def change_training_state(self, state, modality=None, lr=None):
+        """Enter ``state`` (``stages.TrainingState`` or its name; ``None`` returns to the plain step) for ``modality``
+        (default: the current one).  Call it between steps, never inside a phase.  The contract (parity with the thesis's
+        state machine is unpinned: it is not in the reference's ``src/``):
+
+        * ``PRETRAIN``: everything trainable at ``self.lr`` (a label for the auto-encoder run; the caller picks ``'dwi-tensor'``);
+        * ``TRANSFER``: ``gen.blocks['unet']`` frozen, ``gen.blocks[modality]`` and the whole discriminator trainable, ``self.lr``.
+          The frozen body stays in ``train()`` mode (dropout runs; InstanceNorm has no running statistics);
+        * ``FINE_TUNE``: everything trainable at ``self.fine_tune_lr`` (1e-5, the thesis's rate);
+        * ``lr=`` overrides the state's rate.
+
+        The call sets the modality on the model, the generator and the discriminator; sets the ``requires_grad`` flags, which
+        the per-phase toggles restore from now on instead of setting all of them (Lightning's ``toggle_optimizer`` /
+        ``untoggle_optimizer``); drops both optimisers, so that the next ``optimizers()`` builds fresh ones -- fresh moments --
+        over the trainable parameters at the state's rate; detaches the gradient sinks and the gradient exchange and rebuilds
+        them over the trainable parameters (a frozen parameter is left with ``grad is None`` and no sink); and bumps
+        ``stage_version``, which a captured step (``GraphedTrainingStep``) checks before every replay.
+        e4m3 convolution operands are not supported inside a state (``NotImplementedError``)."""
+        from . import stages
+        state = stages.parse_state(state)
+        modality = self.input_modality if modality is None else modality
+        if state is not None and any(getattr(m, "fp8", False) for m in self.modules()):
+            raise NotImplementedError("training states with e4m3 operands are not built: use bf16 or f32 operands")
+        for table in (getattr(self.gen, "blocks", None), getattr(self.discr, "d1", None)):
+            if table is not None and modality not in table:
+                raise KeyError(f"unknown modality {modality!r} (choose from {[k for k in table if k != 'unet']})")
+        self.input_modality = self.gen.input_modality = self.discr.modality = modality
+        self.training_state = state
+        self.stage_lr = None if state is None else float(stages.stage_lr(state, self.lr, self.fine_tune_lr) if lr is None else lr)
+        frozen = stages.frozen_parameters(state, self.gen)
+        self._frozen = frozenset(id(p) for p in frozen)
+        self._optimizers = None
+        # gradient storage and exchange follow the trainable set
+        sinks = (self.sinks_gen, self.sinks_discr)
+        auto = [s.auto_launch for s in sinks if s is not None]
+        for s in sinks:
+            if s is not None:
+                s.detach()
+        self.sinks_gen = self.sinks_discr = None
+        syncs = (self.grad_sync_gen, self.grad_sync_discr)
+        for s in syncs:
+            if s is not None:
+                s.remove()
+        for p in self.parameters():
+            p.requires_grad_(id(p) not in self._frozen)
+        for p in frozen:
+            p.grad = None
+        if auto and self._sink_cfg is not None:
+            self.enable_grad_sinks(*self._sink_cfg)
+            self.sinks_gen.auto_launch = self.sinks_discr.auto_launch = auto[0]
+        if syncs[0] is not None:
+            from . import ddp
+            self.grad_sync_gen = ddp.GradSync(ddp.used_parameters(self.gen, modality, self._frozen), syncs[0].bucket_mb, syncs[0].group)
+            self.grad_sync_discr = ddp.GradSync(ddp.used_parameters(self.discr, modality, self._frozen), syncs[1].bucket_mb,
+                                                syncs[1].group)
+        self.stage_version += 1
+        return self
 
     def optimizers(self):
         if self._optimizers is None:
@@ -200,10 +275,12 @@ class bSSFPToDWITensorModel(nn.Module):
             from .functional import repack_weights
             repack_weights(module)
 
-    @staticmethod
-    def _toggle(module: nn.Module, flag: bool):
+    def _toggle(self, module: nn.Module, flag: bool):
+        """``toggle_optimizer`` (flag False: the network takes no gradient in this phase) / ``untoggle_optimizer`` (flag True: the
+        flags are RESTORED -- whatever the training state keeps frozen stays frozen; without a state that is True for all)"""
+        frozen = self._frozen
         for p in module.parameters():
-            p.requires_grad_(flag)
+            p.requires_grad_(flag and id(p) not in frozen)
 
     # ------------------------------------------------------------------ gradient storage / exchange
     def enable_grad_sinks(self, group=None, distributed: bool = False, force_collectives: bool = False) -> bool:
@@ -226,10 +303,12 @@ class bSSFPToDWITensorModel(nn.Module):
         if not (isinstance(self.gen, Generator) and isinstance(self.discr, Discriminator) and next(self.gen.parameters()).is_cuda):
             return False
         from .gradsink import GradBuckets
-        self.sinks_gen = GradBuckets(backward_stages(self.gen, self.input_modality), group, uses_per_phase=1,
+        # (the frozen parameters of a training state are in no bucket: nothing is stored or exchanged for them)
+        self.sinks_gen = GradBuckets(backward_stages(self.gen, self.input_modality, self._frozen), group, uses_per_phase=1,
                                      distributed=distributed, force_collectives=force_collectives)
-        self.sinks_discr = GradBuckets(backward_stages(self.discr, self.input_modality), group, uses_per_phase=2,
+        self.sinks_discr = GradBuckets(backward_stages(self.discr, self.input_modality, self._frozen), group, uses_per_phase=2,
                                        distributed=distributed, force_collectives=force_collectives)
+        self._sink_cfg = (group, distributed, force_collectives)
         return True
 
     def _finish_grads(self, which: str):
@@ -506,6 +585,7 @@ class GraphedTrainingStep:
         # k-th step (0 = never; the buffers are ~8 KB, the broadcast runs between two graph replays)
         self.broadcast_buffers_every = broadcast_buffers_every if self.world > 1 else 0
         self.step_index = 0
+        self.stage_version = getattr(model, "stage_version", 0)     # the capture holds this state's launches and optimisers
         if model.grad_sync_gen is not None or model.grad_sync_discr is not None:
             raise RuntimeError("GraphedTrainingStep does its own gradient exchange: do not ddp.attach() the model")
         if self.segmented:
@@ -689,7 +769,15 @@ class GraphedTrainingStep:
             if k in self.batch and isinstance(v, dict) and DATA in v:
                 self.batch[k][DATA].copy_(v[DATA], non_blocking=True)
 
+    def stale(self) -> bool:
+        """The model's training state changed after the capture (``change_training_state``): the graph still holds the old
+        state's weight-gradient launches and updates the old optimisers' moments"""
+        return getattr(self.model, "stage_version", 0) != self.stage_version
+
     def __call__(self, instance: int = 0, after=None):
+        if self.stale():
+            raise RuntimeError("GraphedTrainingStep: the model's training state changed after this step was captured "
+                               f"(stage_version {self.stage_version} -> {self.model.stage_version}); capture a new one")
         if self.broadcast_buffers_every:
             from . import ddp
             ddp.broadcast_buffers(self.model, every=self.broadcast_buffers_every, step=self.step_index, group=self.group)
@@ -714,4 +802,6 @@ def synthetic_batch(n: int, s, seed: int, modality: str = "bssfp", device="cpu")
     x = torch.rand(n, cin, *s, generator=g)
     y = torch.rand(n, 6, *s, generator=g)
     x, y = x.to(device), y.to(device)
-    return {modality: {DATA: x}, "dwi-tensor_orig": {DATA: y}, "dwi-tensor": {DATA: y}}
+    batch = {"dwi-tensor_orig": {DATA: y}, "dwi-tensor": {DATA: y}}
+    batch[modality] = {DATA: x}     # (last: with 'dwi-tensor' -- the auto-encoder of the PRETRAIN stage -- the input is a tensor of its own)
+    return batch

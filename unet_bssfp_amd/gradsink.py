@@ -67,7 +67,9 @@ class GradBuckets:
         on: a model that was never attached must not start collectives just because a process group exists -- its
         parameters were never broadcast and other ranks may not be training at all).
         ``force_collectives``: issue the all-reduces even on a one-rank group (rehearsal of the RCCL + hipGraph interplay
-        on a single GPU: ``bench.py --force-collectives``)."""
+        on a single GPU: ``bench.py --force-collectives``).
+        An empty parameter list keeps its bucket index (no buffer, never exchanged): the staged backward addresses its
+        buckets by stage, and a training state may freeze a whole stage (stages.py)."""
         self.group = group
         self.world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
         self.exchange = self.world > 1 or (force_collectives and distributed and dist.is_initialized())
@@ -89,6 +91,10 @@ class GradBuckets:
                     seen.add(id(p))
                     uniq.append(p)
             if not uniq:
+                self.params.append([])
+                self.flat.append(None)
+                self._pending.append(0)
+                self._work.append(None)
                 continue
             dev = uniq[0].device
             flat = torch.zeros(sum(p.numel() for p in uniq), dtype=torch.float32, device=dev)
@@ -151,7 +157,7 @@ class GradBuckets:
         """Sum bucket ``b`` over the ranks, asynchronously: RCCL runs on its own stream and first waits for the
         kernels already enqueued on the current stream (torch.distributed semantics); the backward kernels enqueued
         afterwards overlap it."""
-        if not self.exchange or self._work[b] is not None:
+        if not self.exchange or self._work[b] is not None or self.flat[b] is None:
             return
         _join_side_stream()                          # weight-gradient kernels on the side stream write into this bucket
         op = dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM
@@ -167,6 +173,8 @@ class GradBuckets:
                 self.launch(b)
         inv = 1.0 / self.world
         for b, w in enumerate(self._work):
+            if w is None:                             # (an empty bucket: nothing was exchanged)
+                continue
             w.wait()                                  # stream-level wait with nccl, host wait with gloo
             if not self._avg and self.world > 1:
                 self.flat[b].mul_(inv)                # (gloo only: with RCCL the collective itself averages)

@@ -587,9 +587,10 @@ class BasicUNet(_Mi355Module):
         return Fn.UnpackFn.apply(z, self.out_channels)
 
 
-def backward_stages(net: nn.Module, modality):
+def backward_stages(net: nn.Module, modality, frozen=()):
     """(late, early) parameter lists of a Generator / Discriminator for the two backward stages cut at
-    ``Fn.StageBoundary`` (the unused modality heads are in neither list: src/model.py:29-34, 74-78)."""
+    ``Fn.StageBoundary`` (the unused modality heads are in neither list: src/model.py:29-34, 74-78).
+    ``frozen``: id() of the parameters a training state keeps fixed (stages.py): in neither list either."""
     if isinstance(net, Generator):
         unet = net.blocks["unet"]
         early_mods = [net.blocks[modality], unet.conv_0, unet.down_1, unet.down_2]
@@ -599,8 +600,8 @@ def backward_stages(net: nn.Module, modality):
         late_mods = [net.d3, net.d4, net.d5, net.final]
     else:
         raise TypeError("backward_stages: Generator or Discriminator expected")
-    late = [p for m in reversed(late_mods) for p in reversed(list(m.parameters()))]
-    early = [p for m in reversed(early_mods) for p in reversed(list(m.parameters()))]
+    late = [p for m in reversed(late_mods) for p in reversed(list(m.parameters())) if id(p) not in frozen]
+    early = [p for m in reversed(early_mods) for p in reversed(list(m.parameters())) if id(p) not in frozen]
     return late, early
 
 

@@ -18,8 +18,9 @@ What the loop is made of:
 * ``PatchQueue.state_dict``  the feed's state at an epoch boundary (data.py).
 * ``EarlyStopping``, ``ModelCheckpoint``, ``Trainer``  below.
 
-Not built: Lightning's two sanity validation batches before the first epoch, the W&B logger, the thesis's TRANSFER /
-FINE_TUNE training states, and resuming in the middle of an epoch (a checkpoint is written at epoch boundaries only).
+Not built: Lightning's two sanity validation batches before the first epoch, the W&B logger, and resuming in the middle of
+an epoch (a checkpoint is written at epoch boundaries only).  The thesis's PRETRAIN / TRANSFER / FINE_TUNE states are in
+``stages.py`` and ``train.train_staged``; a captured step is dropped when the model's state changes.
 Multi-rank ``fit`` is unmeasured on hardware.
 """
 from __future__ import annotations
@@ -196,6 +197,8 @@ class ModelCheckpoint:
       ``stamp = str(datetime.now())`` taken at construction; ``-v1``, ``-v2``, ... is appended if the name exists.
       ``filename`` replaces the part in front of the stamp with a Lightning-style template (``'{epoch:02d}-{val_loss:.4f}'``:
       every ``{name`` becomes ``name={name``; ``{modality}`` is replaced as is) and then ``stamp`` defaults to ``''``;
+      a model in a training state (stages.py) gets the state in front, as the reference's files have it (src/train.py):
+      ``TrainingState.TRANSFER-pc-bssfp-epoch=31-val_loss=...``;
     * ``save_last`` also writes ``last.ckpt`` every epoch;
     * ``best_model_path``, ``best_model_score``, ``best_k_models`` ({path: score}) as in Lightning.
 
@@ -225,6 +228,9 @@ class ModelCheckpoint:
         values.update(epoch=trainer.current_epoch, modality=getattr(model, "input_modality", "model"))
         try:
             base = template.format(**values) + self.stamp
+            state = getattr(model, "training_state", None)
+            if state is not None:
+                base = f"{state}-{base}"
         except KeyError as e:
             raise RuntimeError(f"ModelCheckpoint: {e} is not among the epoch's metrics {sorted(trainer.callback_metrics)}")
         path, v = os.path.join(self.dirpath, base + ".ckpt"), 0
@@ -309,8 +315,8 @@ class Trainer:
     transform list is as free of host reads as its stages are.
 
     A trainer may ``fit`` more than once.  The captured step of an earlier call is kept only for the same model, batch and
-    patch shape and only while every tensor it updates is still the one it captured; ``fit(ckpt_path=...)``, another model
-    or a checkpoint loaded in between drop it, and it is rebuilt at the first epoch.
+    patch shape and only while every tensor it updates is still the one it captured; ``fit(ckpt_path=...)``, another model,
+    a checkpoint loaded in between or a ``change_training_state`` drop it, and it is rebuilt at the first epoch.
 
     Checkpoints are ``checkpoint.checkpoint_dict(model, epoch, global_step)`` with ``callbacks`` filled
     (``{'EarlyStopping': ..., 'ModelCheckpoint': ...}``) and ``mi355`` extended by ``train_queue`` / ``val_queue`` states and the
@@ -413,13 +419,14 @@ class Trainer:
     @staticmethod
     def _graph_key(model, queue):
         """What a captured step is tied to: the model object, the batch and patch shape, and the ADDRESSES of every parameter,
-        optimiser moment and device step counter (``FusedAdamW.load_state_dict`` replaces the latter two with new tensors)."""
+        optimiser moment and device step counter (``FusedAdamW.load_state_dict`` replaces the latter two with new tensors), and
+        the model's ``stage_version`` (``change_training_state`` changes which gradients a step computes)."""
         ptrs = [p.data_ptr() for p in model.parameters()]
         for o in model.optimizers():
             for st in o.state.values():
                 ptrs += [v.data_ptr() for v in st.values() if isinstance(v, torch.Tensor)]
             ptrs += [t.data_ptr() for t in getattr(o, "_step_dev", {}).values()]
-        return (id(model), model.batch_size, tuple(getattr(queue, "patch_size", ())), tuple(ptrs))
+        return (id(model), model.batch_size, tuple(getattr(queue, "patch_size", ())), tuple(ptrs), getattr(model, "stage_version", 0))
 
     def _drop_graph(self):
         self.graphed_step, self._graph_for = None, None
@@ -431,7 +438,7 @@ class Trainer:
         or by the caller); otherwise it is dropped and rebuilt at the first epoch.  A kept graph's step base is read afresh."""
         if self.graphed_step is None:
             return
-        if self.graphed_step.model is not model or self._graph_for != self._graph_key(model, queue):
+        if self.graphed_step.model is not model or self.graphed_step.stale() or self._graph_for != self._graph_key(model, queue):
             self._drop_graph()
             return
         self._steps_base = [self._device_steps(o) for o in model.optimizers()]
