@@ -996,6 +996,19 @@ def test_generator_output_seam_equals_unpack_add_pack(hip, which):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("drop_p", [0.0, 0.05])
 def test_norm_backward_forms_the_maxpool_gradient_itself(hip, dtype, drop_p):
+    _norm_backward_forms_the_maxpool_gradient_itself(dtype, drop_p, levels=False)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("drop_p", [0.0, 0.05])
+def test_norm_backward_forms_the_maxpool_gradient_itself_with_tied_activations(hip, dtype, drop_p):
+    """The same with z drawn from four levels per channel: the activations tie inside most windows, so the norm kernels' copy of
+    the window scan must resolve ties by the rule of the max-pool kernels (first in scan order).  Its own test name, so that the
+    cases above keep theirs."""
+    _norm_backward_forms_the_maxpool_gradient_itself(dtype, drop_p, levels=True)
+
+
+def _norm_backward_forms_the_maxpool_gradient_itself(dtype, drop_p, levels):
     """Fn.LazyPool: MaxPool3d(2)'s backward (+ the skip connection's gradient) formed per row inside the producing norm + act
     node's backward kernels from the window positions the forward max-pool recorded (mi355_maxpool2_fwd_idx,
     mi355_normact_desc::pool_idx) -- bit-identical to the max-pool backward launch followed by the plain kernels: ops level
@@ -1004,7 +1017,12 @@ def test_norm_backward_forms_the_maxpool_gradient_itself(hip, dtype, drop_p):
     from unet_bssfp_amd import functional as Fn, ops
     g = torch.Generator().manual_seed(29)
     n, c, sp = 2, 32, (8, 12, 32)
-    z = to_act(q(torch.randn(n, c, *sp, generator=g) * 1.5 + 0.3, dtype), dtype)
+    z_cpu = torch.randn(n, c, *sp, generator=g) * 1.5 + 0.3
+    if levels:                                             # four values per channel: ties inside most 2x2x2 windows
+        table = torch.randn(c, 4, generator=g) * 1.5 + 0.3
+        pick = torch.randint(0, 4, (n, c, *sp), generator=g)
+        z_cpu = table.view(1, c, 1, 1, 1, 4).expand(n, c, *sp, 4).gather(5, pick[..., None])[..., 0]
+    z = to_act(q(z_cpu, dtype), dtype)
     gamma, beta = (torch.rand(c, generator=g) + 0.5).to(DEV), (torch.rand(c, generator=g) - 0.5).to(DEV)
     rows = sp[0] * sp[1] * sp[2]
     part, ppg = ops.channel_stats(z, n)

@@ -295,7 +295,9 @@ def _worker_transfer(rank, world, port, q):
         gathered = [torch.zeros_like(digest) for _ in range(world)]
         dist.all_gather(gathered, digest)
         assert all(torch.equal(g, gathered[0]) for g in gathered), "ranks diverged after the step"
-        q.put((rank, "ok" if untouched else "FAIL: a frozen parameter moved", grads))
+        # as numpy arrays: pickled by value.  A tensor crosses the queue as a file descriptor served by THIS process, which may be
+        # gone (destroy_process_group, exit) before the parent unpickles it: FileNotFoundError in q.get, now and then
+        q.put((rank, "ok" if untouched else "FAIL: a frozen parameter moved", {n: g.numpy() for n, g in grads.items()}))
     except Exception as e:  # noqa: BLE001
         import traceback
         q.put((rank, f"FAIL: {e!r} {traceback.format_exc()}", None))
@@ -324,7 +326,7 @@ def test_transfer_on_two_gloo_ranks_exchanges_the_trainable_set_only():
         torch.set_num_threads(threads)
     for n, want in total.items():
         for r in range(2):
-            torch.testing.assert_close(res[r][2][n], want / 2, rtol=1e-5, atol=1e-7, msg=lambda m: f"rank {r} {n}: {m}")
+            torch.testing.assert_close(torch.from_numpy(res[r][2][n]), want / 2, rtol=1e-5, atol=1e-7, msg=lambda m: f"rank {r} {n}: {m}")
 
 
 def _single_process_head_gradients():

@@ -13,7 +13,11 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 struct bf16_t { uint16_t v; };
 // OCP e4m3 operand of the fp8 convolution path (per-tensor scaled: value * 224 / amax)
 struct fp8_t { uint8_t v; };
-__device__ __forceinline__ float fp8_clamp(float f) { return fminf(fmaxf(f, -448.f), 448.f); }
+// saturates at +-448 (+-inf included); a NaN stays a NaN (e4m3 0x7f / 0xff).  The clamp alone -- one v_med3_f32 -- stored a NaN
+// as -448, and a diverged run looked finite to its fp8 convolutions.  The amax passes (fmaxf) keep ignoring NaN: a NaN operand
+// reaches the convolution's output, not the scale.  v_cmp_u + v_cndmask per value; two compares and selects, and one unordered
+// compare per pair with a branch, measured no faster.
+__device__ __forceinline__ float fp8_clamp(float f) { return f != f ? f : fminf(fmaxf(f, -448.f), 448.f); }
 // two floats -> two e4m3 bytes in the low (hi = false) or high half of `old`
 __device__ __forceinline__ uint32_t cvt_pk_fp8(float a, float b, uint32_t old, bool hi) {
   return hi ? (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(a), fp8_clamp(b), (int)old, true)

@@ -4,6 +4,9 @@
 namespace {
 
 // ------------------------------------------------------------------ fp8 operand preparation
+// NaN policy: every amax here (and amax_commit's callers) is a chain of fmaxf, which drops a NaN operand -- the scale stays the
+// maximum of the finite values and +-inf -- while the cast keeps the NaN element a NaN byte (common.h: fp8_clamp), so it
+// reaches the convolution's output.
 __global__ __launch_bounds__(256) void amax_f32_kernel(const float* __restrict__ x, long long n, float* out) {
   float m = 0.f;
   const long long stride = (long long)gridDim.x * 256 * 4;

@@ -155,9 +155,11 @@ static int pack_impl(const float* src, void* dst, int32_t n, int32_t c, int64_t 
   MI355_REQUIRE(coff % epv == 0 && zero_to <= ld && (zero_to - coff) % epv == 0 && zero_to - coff >= c + c1 && ld % epv == 0,
                 "pack: channel window [%d,%d) of ld %d must be 16-byte aligned and hold c=%d", coff, zero_to, ld, c);
   const int pieces = (zero_to - coff) / epv;
-  if (zero_to - coff <= 64 && v >= 4096) {                // LDS-tiled form: whole-line reads, whole-row writes
-    const int es = dtype == MI355_DT_F32 ? 4 : 2;
-    const size_t lds = (size_t)256 * ((zero_to - coff) * es + 4);
+  const int es = dtype == MI355_DT_F32 ? 4 : 2;
+  const size_t lds = (size_t)256 * ((zero_to - coff) * es + 4);
+  // LDS-tiled form: whole-line reads, whole-row writes.  Its tile must fit the 64 KB a launch gets without a raised limit
+  // (common.h: raise_lds_limit): an f32 window of 64 channels (66 560 bytes; no caller has one) takes the piece-per-lane form.
+  if (zero_to - coff <= 64 && v >= 4096 && lds <= 64 * 1024) {
     dim3 grid((unsigned)((v + 255) / 256), n);
     for_dtype(dtype, [&](auto t) { pack_tile_kernel<decltype(t)><<<grid, dim3(256), lds, (hipStream_t)stream>>>(src, (decltype(t)*)dst, c, (long long)v, ld, coff, zero_to, q, src1, c1); });
     return mi355_check_launch("pack");
