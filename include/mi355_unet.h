@@ -330,6 +330,14 @@ typedef struct mi355_normact_desc {
    * ldpy elements) and pool_widx (bytes, as mi355_maxpool2_fwd_idx) on the sd x sh x sw grid (even extents; a group is one sample
    * or the whole batch); plain layouts, no q8 / fy.  Bit-identical to mi355_normact_fwd + mi355_maxpool2_fwd_idx. */
   void* pool_y; int32_t ldpy; uint8_t* pool_widx;
+  /* optional: PReLU with ONE trained slope (torch.nn.PReLU(num_parameters=1)).  alpha = DEVICE pointer to the slope, read by every
+   * kernel at launch time instead of `slope` (an optimiser updates it in place, a replayed hipGraph sees the update); NULL: `slope`
+   * by value.  Backward, when dalpha is given: dalpha[0] (+)= sum over every element with u <= 0 of da * u, u = Dropout(Norm(z)) --
+   * formed by the launches that reduce dgamma / dbeta (mi355_normact_bwd_reduce + mi355_normact_bwd_finalize_prelu, or
+   * mi355_normact_small_bwd, whose `accumulate` then governs dalpha too) plus one single-workgroup launch; f32 partials per thread,
+   * f64 in a fixed order from there on, no atomics.  dalpha_part = scratch: bwd_reduce writes [groups * blocks_per_group][c] floats,
+   * small_bwd [groups][c] DOUBLES (8-byte aligned). */
+  const float* alpha; float* dalpha; void* dalpha_part;
 } mi355_normact_desc;
 int mi355_normact_fwd(const mi355_normact_desc* d, void* stream);
 int mi355_normact_bwd_reduce(const mi355_normact_desc* d, void* stream);
@@ -342,6 +350,12 @@ int mi355_normact_bwd_finalize(const float* part, int32_t blocks_per_group, int3
 int mi355_normact_bwd_finalize_into(const float* part, int32_t blocks_per_group, int32_t groups, int32_t c,
                                     float* sums, float* dgamma, float* dbeta, int32_t n_affine, int32_t accumulate,
                                     void* stream);
+/* the same for a node whose bwd_reduce also wrote the slope-gradient partials apart[groups * blocks_per_group][c]
+ * (mi355_normact_desc::dalpha_part): per-channel f64 totals go to alpha_ch[c] (scratch, doubles), and a second, single-workgroup
+ * launch adds them in a fixed order into dalpha[0] (`accumulate` as for the affine gradients; dgamma / dbeta may be NULL). */
+int mi355_normact_bwd_finalize_prelu(const float* part, const float* apart, int32_t blocks_per_group, int32_t groups, int32_t c,
+                                     float* sums, float* dgamma, float* dbeta, int32_t n_affine, int32_t accumulate,
+                                     double* alpha_ch, float* dalpha, void* stream);
 int mi355_normact_bwd_apply(const mi355_normact_desc* d, void* stream);
 
 /* Norm + dropout + LeakyReLU of a SMALL tensor (the 16^3 / 8^3 U-Net levels, the last PatchGAN blocks: src/model.py:22-28,

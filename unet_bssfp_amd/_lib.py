@@ -65,7 +65,8 @@ class NormActDesc(C.Structure):
                 ("gz", _vp), ("ldgz", _i32), ("gw", _vp), ("gw_ld", _i32), ("gk", _i32),
                 ("fy", _vp), ("ldfy", _i32), ("fcp", _i32), ("fbias", _vp), ("skip_a", _i32),
                 ("pool_idx", _vp), ("pool_dy", _vp), ("ldpdy", _i32),
-                ("pool_y", _vp), ("ldpy", _i32), ("pool_widx", _vp)]
+                ("pool_y", _vp), ("ldpy", _i32), ("pool_widx", _vp),
+                ("alpha", _vp), ("dalpha", _vp), ("dalpha_part", _vp)]
 
 
 class QueueLoad(C.Structure):
@@ -125,6 +126,7 @@ _SIGNATURES = {
     "mi355_normact_bwd_reduce": (C.c_int, [C.POINTER(NormActDesc), _vp]),
     "mi355_normact_bwd_finalize": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mi355_normact_bwd_finalize_into": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "mi355_normact_bwd_finalize_prelu": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "mi355_normact_bwd_apply": (C.c_int, [C.POINTER(NormActDesc), _vp]),
     "mi355_normact_small_fwd": (C.c_int, [C.POINTER(NormSmallDesc), _vp]),
     "mi355_normact_small_bwd": (C.c_int, [C.POINTER(NormSmallDesc), _vp]),

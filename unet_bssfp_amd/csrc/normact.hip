@@ -9,35 +9,43 @@ constexpr int kRowsPerStatBlock = 2048;
 
 // ------------------------------------------------------------------ channel statistics
 // One block = up to kRowsPerStatBlock rows of one group.  Thread = (row-in-pass, 16-B piece).
-// f(row values) is supplied by the functor; sums of two quantities per channel are produced.
-template <typename T, typename F>
+// f(row values) is supplied by the functor; sums of two quantities per channel are produced -- or of three (out2: the PReLU slope
+// gradient's share, which the functor adds into s2).
+template <typename T, bool THIRD = false, typename F>
 __device__ __forceinline__ void block_channel_sums(int c, long long row_begin, long long row_end, F f,
-                                                   float* out0, float* out1) {
+                                                   float* out0, float* out1, float* out2 = nullptr) {
   constexpr int EPV = Elem<T>::kPer16B;
-  __shared__ float red[256 * 16];
+  constexpr int W = THIRD ? 24 : 16;       // floats of LDS per thread
+  __shared__ float red[256 * W];
   const int lpr = c / EPV;                 // 16-B pieces per row (<= 128)
   const int rpp = 256 / lpr;               // rows per pass
   const int piece = threadIdx.x % lpr, rsub = threadIdx.x / lpr;
-  float s0[EPV], s1[EPV];
+  float s0[EPV], s1[EPV], s2[EPV];
 #pragma unroll
-  for (int j = 0; j < EPV; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
+  for (int j = 0; j < EPV; ++j) { s0[j] = 0.f; s1[j] = 0.f; s2[j] = 0.f; }
   if (rsub < rpp)
-    for (long long row = row_begin + rsub; row < row_end; row += rpp) f(row, piece * EPV, s0, s1);
+    for (long long row = row_begin + rsub; row < row_end; row += rpp) {
+      if constexpr (THIRD) f(row, piece * EPV, s0, s1, s2);
+      else f(row, piece * EPV, s0, s1);
+    }
 #pragma unroll
   for (int j = 0; j < EPV; ++j) {
-    red[threadIdx.x * 16 + j] = s0[j];
-    red[threadIdx.x * 16 + 8 + j] = s1[j];
+    red[threadIdx.x * W + j] = s0[j];
+    red[threadIdx.x * W + 8 + j] = s1[j];
+    if constexpr (THIRD) red[threadIdx.x * W + 16 + j] = s2[j];
   }
   __syncthreads();
   for (int ch = threadIdx.x; ch < c; ch += 256) {
     const int p = ch / EPV, j = ch % EPV;
-    float t0 = 0.f, t1 = 0.f;
+    float t0 = 0.f, t1 = 0.f, t2 = 0.f;
     for (int q = 0; q < rpp; ++q) {
-      t0 += red[(q * lpr + p) * 16 + j];
-      t1 += red[(q * lpr + p) * 16 + 8 + j];
+      t0 += red[(q * lpr + p) * W + j];
+      t1 += red[(q * lpr + p) * W + 8 + j];
+      if constexpr (THIRD) t2 += red[(q * lpr + p) * W + 16 + j];
     }
     out0[ch] = t0;
     out1[ch] = t1;
+    if constexpr (THIRD) out2[ch] = t2;
   }
 }
 
@@ -170,6 +178,7 @@ __global__ __launch_bounds__(256) void normact_fwd_kernel(const NormActArgs q) {
   T* ab = reinterpret_cast<T*>(q.a) + (long long)g * q.rows_per_group * q.lda;
   const long long stride = (long long)gridDim.x * rpp;
   const float sc8 = q.q8 ? fp8_scale_of(q.q_use) : 1.f;
+  const float slope = act_slope(q);
   float m8 = 0.f;
   for (long long row = (long long)blockIdx.x * rpp + rsub; row < q.rows_per_group; row += stride) {
     Vec16<T> v;
@@ -185,7 +194,7 @@ __global__ __launch_bounds__(256) void normact_fwd_kernel(const NormActArgs q) {
     for (int j = 0; j < EPV; ++j) {
       float t = v.f[j] * sc[j] + sh[j];
       if constexpr (DROP) t = (keep >> j) & 1u ? t * q.drop_scale : 0.f;
-      v.f[j] = t > 0.f ? t : t * q.slope;
+      v.f[j] = t > 0.f ? t : t * slope;
     }
     if (q.s2d_a.d) {
       long long srow; int blk, border;
@@ -237,6 +246,7 @@ __global__ __launch_bounds__(256) void normact_pool_fwd_kernel(const NormActArgs
   const int pooled = od_ * oh_ * ow_;
   const T* zb = reinterpret_cast<const T*>(q.z);
   T* ab = reinterpret_cast<T*>(q.a);
+  const float slope = act_slope(q);
   for (int o = blockIdx.x * vpp + vsub; o < pooled; o += gridDim.x * vpp) {
     const int ow = o % ow_, t = o / ow_, oh = t % oh_, od = t / oh_;
     Vec16<T> m;
@@ -262,7 +272,7 @@ __global__ __launch_bounds__(256) void normact_pool_fwd_kernel(const NormActArgs
           for (int j = 0; j < EPV; ++j) {
             float t2 = v.f[j] * sc[j] + sh[j];
             if constexpr (DROP) t2 = (keep >> j) & 1u ? t2 * q.drop_scale : 0.f;
-            t2 = t2 > 0.f ? t2 : t2 * q.slope;
+            t2 = t2 > 0.f ? t2 : t2 * slope;
             if constexpr (sizeof(T) == 2) t2 = bf16_bits_to_f32(f32_to_bf16_bits(t2));      // the stored value
             v.f[j] = t2;
           }
@@ -335,6 +345,7 @@ __global__ __launch_bounds__(256) void normact_fwd_final32_kernel(const NormActA
   bf16_t* ab = reinterpret_cast<bf16_t*>(q.a) + (long long)g * q.rows_per_group * q.lda;
   bf16_t* yb = reinterpret_cast<bf16_t*>(q.fy) + (long long)g * q.rows_per_group * q.ldfy;
   const long long stride = (long long)gridDim.x * 64;
+  const float slope = act_slope(q);
   // (the next block's piece is loaded before this block's is processed: load -> math -> MFMA -> store is one dependent chain per wave)
   const long long first = (long long)blockIdx.x * 64 + wave * 16;
   uint4 zn = make_uint4(0u, 0u, 0u, 0u);
@@ -359,7 +370,7 @@ __global__ __launch_bounds__(256) void normact_fwd_final32_kernel(const NormActA
     for (int j = 0; j < 8; ++j) {
       float x = v.f[j] * sc[j] + sh[j];
       if constexpr (DROP) x = (keep >> j) & 1u ? x * q.drop_scale : 0.f;
-      v.f[j] = x > 0.f ? x : x * q.slope;
+      v.f[j] = x > 0.f ? x : x * slope;
     }
     unsigned w[4];
 #pragma unroll
@@ -437,7 +448,8 @@ __device__ __forceinline__ void pooled_da(const NormActArgs& q, long long grow, 
   }
 }
 // IMPL: 0 = da is a tensor, 1 = implicit 1x1x1 data gradient (gz), 2 = implicit max-pool backward (pool_idx)
-template <typename T, bool DROP, int IMPL = 0>
+// PRELU: a third sum per channel, the slope gradient's share, into q.dalpha_part[group * blocks + block][c]
+template <typename T, bool DROP, int IMPL = 0, bool PRELU = false>
 __global__ __launch_bounds__(256) void normact_bwd_reduce_kernel(const NormActArgs q) {
   constexpr int EPV = Elem<T>::kPer16B;
   const int g = blockIdx.y, b = blockIdx.x;
@@ -453,8 +465,10 @@ __global__ __launch_bounds__(256) void normact_bwd_reduce_kernel(const NormActAr
   const unsigned long long seed = DROP ? eff_seed(q.seed, q.seed_ptr) : 0ull;
   __shared__ uint4 wtab[IMPL == 1 ? kImplicitMaxC : 1];
   if constexpr (IMPL == 1) fill_implicit_w(q, wtab);
-  block_channel_sums<T>(q.c, r0, r1,
-      [&](long long row, int ch0, float* s0, float* s1) {
+  const float slope = act_slope(q);
+  float* aout = PRELU ? reinterpret_cast<float*>(q.dalpha_part) + ((long long)g * q.blocks_per_group + b) * q.c : nullptr;
+  block_channel_sums<T, PRELU>(q.c, r0, r1,
+      [&](long long row, int ch0, float* s0, float* s1, float* s2 = nullptr) {
         Vec16<T> zv, dv;
         zv.load(zb + row * q.ldz + ch0);
         if constexpr (IMPL == 1) implicit_da<T, EPV>(q, (long long)g * q.rows_per_group + row, wtab, ch0, dv);
@@ -465,22 +479,46 @@ __global__ __launch_bounds__(256) void normact_bwd_reduce_kernel(const NormActAr
         if constexpr (DROP) keep = drop_keep_mask<EPV>(seed, ((unsigned long long)g * q.rows_per_group + row) * q.c + ch0, q.thr16);
 #pragma unroll
         for (int j = 0; j < EPV; ++j) {
-          float gv, xh;
-          bwd_elem<DROP>(q, (keep >> j) & 1u, k.mu[j], k.rs[j], k.ga[j], k.be[j], zv.f[j], dv.f[j], gv, xh);
+          float gv, xh, at;
+          bwd_elem<DROP>(q, slope, (keep >> j) & 1u, k.mu[j], k.rs[j], k.ga[j], k.be[j], zv.f[j], dv.f[j], gv, xh, at);
           s0[j] += gv;
           s1[j] += gv * xh;
+          if constexpr (PRELU) s2[j] += at;
         }
       },
-      out, out + q.c);
+      out, out + q.c, aout);
 }
 
+// block_sum_parts for ONE quantity per partial, part[k][c] (the slope-gradient partials): same lanes, same order, f64
+__device__ __forceinline__ double block_sum_parts1(const float* __restrict__ part, int nparts, int c, int ch0) {
+  __shared__ double red[16][8];
+  const int cl = threadIdx.x & 7, pl = threadIdx.x >> 3;
+  const int ch = ch0 + cl;
+  double s = 0.0;
+  if (ch < c)
+    for (int k = pl; k < nparts; k += 128) s += (double)part[(long long)k * c + ch];
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) < 8) red[wave][cl] = s;
+  __syncthreads();
+  double a = 0.0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) a += red[w][cl];
+  __syncthreads();
+  return a;
+}
+
+// PRELU: also alpha_ch[ch] = this channel's slope-gradient total over all groups (slope_grad_sum_kernel adds the channels)
+template <bool PRELU>
 __global__ __launch_bounds__(1024) void normact_bwd_finalize_kernel(const float* __restrict__ part, int bpg,
                                                                     int groups, int c, float* __restrict__ sums,
-                                                                    float* dgamma, float* dbeta, int n_affine, int accumulate) {
+                                                                    float* dgamma, float* dbeta, int n_affine, int accumulate,
+                                                                    const float* __restrict__ apart, double* __restrict__ alpha_ch) {
   const int ch0 = blockIdx.x * 8;
   const int ch = ch0 + (int)threadIdx.x;
   const bool owner = threadIdx.x < 8 && ch < c;
-  double tg = 0.0, tb = 0.0;
+  double tg = 0.0, tb = 0.0, ta = 0.0;
   for (int g = 0; g < groups; ++g) {
     double s0, s1;
     block_sum_parts(part + (long long)g * bpg * 2 * c, bpg, c, ch0, s0, s1);
@@ -490,6 +528,10 @@ __global__ __launch_bounds__(1024) void normact_bwd_finalize_kernel(const float*
       tb += s0;
       tg += s1;
     }
+    if constexpr (PRELU) ta += block_sum_parts1(apart + (long long)g * bpg * c, bpg, c, ch0);
+  }
+  if constexpr (PRELU) {
+    if (owner) alpha_ch[ch] = ch < n_affine ? ta : 0.0;      // (padded channels: u = 0, but their da is whatever the producer left)
   }
   if (owner && ch < n_affine) {
     if (dgamma) dgamma[ch] = accumulate ? dgamma[ch] + (float)tg : (float)tg;
@@ -525,6 +567,7 @@ __global__ __launch_bounds__(256, IMPL == 1 ? 5 : 1) void normact_bwd_apply_kern
   T* ob = reinterpret_cast<T*>(q.dz) + (long long)g * q.rows_per_group * q.lddz;
   const long long stride = (long long)gridDim.x * rpp;
   const float sc8 = q.q8 ? fp8_scale_of(q.q_use) : 1.f;
+  const float slope = act_slope(q);
   float m8 = 0.f;
   for (long long row = (long long)blockIdx.x * rpp + rsub; row < q.rows_per_group; row += stride) {
     Vec16<T> zv, dv;
@@ -546,7 +589,7 @@ __global__ __launch_bounds__(256, IMPL == 1 ? 5 : 1) void normact_bwd_apply_kern
 #pragma unroll
     for (int j = 0; j < EPV; ++j) {
       float gv, xh;
-      bwd_elem<DROP>(q, (keep >> j) & 1u, k.mu[j], k.rs[j], k.ga[j], k.be[j], zv.f[j], dv.f[j], gv, xh);
+      bwd_elem<DROP>(q, slope, (keep >> j) & 1u, k.mu[j], k.rs[j], k.ga[j], k.be[j], zv.f[j], dv.f[j], gv, xh);
       zv.f[j] = kk[j] * (gv - m0[j] - xh * m1[j]);
     }
     zv.store(ob + row * q.lddz + ch0);
@@ -662,7 +705,17 @@ int mi355_normact_bwd_reduce(const mi355_normact_desc* d, void* stream) {
   if (rc) return rc;
   MI355_REQUIRE((d->gz || d->pool_idx || (d->da && d->ldda >= d->c)) && d->part && d->blocks_per_group > 0, "normact_bwd_reduce: bad argument");
   dim3 grid(d->blocks_per_group, d->groups);
-  if (q.gz) {                 // (bf16 only, and never together with pool_idx: fill_normact)
+  if (d->dalpha) {            // PReLU with a slope gradient to form: the same launch, a third sum per channel
+    if (q.gz) {
+      if (q.thr16) normact_bwd_reduce_kernel<bf16_t, true, 1, true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(q);
+      else normact_bwd_reduce_kernel<bf16_t, false, 1, true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(q);
+    } else {
+      for_dtype_drop(d->dtype, q.thr16, [&](auto t, auto drop) {
+        if (q.pool_idx) normact_bwd_reduce_kernel<decltype(t), drop, 2, true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(q);
+        else normact_bwd_reduce_kernel<decltype(t), drop, 0, true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(q);
+      });
+    }
+  } else if (q.gz) {          // (bf16 only, and never together with pool_idx: fill_normact)
     if (q.thr16) normact_bwd_reduce_kernel<bf16_t, true, 1><<<grid, dim3(256), 0, (hipStream_t)stream>>>(q);
     else normact_bwd_reduce_kernel<bf16_t, false, 1><<<grid, dim3(256), 0, (hipStream_t)stream>>>(q);
   } else {
@@ -683,9 +736,20 @@ int mi355_normact_bwd_finalize_into(const float* part, int32_t blocks_per_group,
                                     float* dgamma, float* dbeta, int32_t n_affine, int32_t accumulate, void* stream) {
   MI355_REQUIRE(part && sums && blocks_per_group > 0 && groups > 0 && c > 0 && n_affine > 0 && n_affine <= c,
                 "normact_bwd_finalize: bad argument");
-  hipLaunchKernelGGL(normact_bwd_finalize_kernel, dim3((c + 7) / 8), dim3(1024), 0, (hipStream_t)stream, part,
-                     blocks_per_group, groups, c, sums, dgamma, dbeta, n_affine, accumulate);
+  hipLaunchKernelGGL(normact_bwd_finalize_kernel<false>, dim3((c + 7) / 8), dim3(1024), 0, (hipStream_t)stream, part,
+                     blocks_per_group, groups, c, sums, dgamma, dbeta, n_affine, accumulate, (const float*)nullptr, (double*)nullptr);
   return mi355_check_launch("normact_bwd_finalize");
+}
+
+int mi355_normact_bwd_finalize_prelu(const float* part, const float* apart, int32_t blocks_per_group, int32_t groups, int32_t c,
+                                     float* sums, float* dgamma, float* dbeta, int32_t n_affine, int32_t accumulate,
+                                     double* alpha_ch, float* dalpha, void* stream) {
+  MI355_REQUIRE(part && apart && sums && alpha_ch && dalpha && blocks_per_group > 0 && groups > 0 && c > 0 && n_affine > 0 &&
+                n_affine <= c, "normact_bwd_finalize_prelu: bad argument");
+  hipLaunchKernelGGL(normact_bwd_finalize_kernel<true>, dim3((c + 7) / 8), dim3(1024), 0, (hipStream_t)stream, part,
+                     blocks_per_group, groups, c, sums, dgamma, dbeta, n_affine, accumulate, apart, alpha_ch);
+  hipLaunchKernelGGL(slope_grad_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)alpha_ch, c, dalpha, accumulate);
+  return mi355_check_launch("normact_bwd_finalize_prelu");
 }
 
 int mi355_normact_bwd_apply(const mi355_normact_desc* d, void* stream) {

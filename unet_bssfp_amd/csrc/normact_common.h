@@ -1,4 +1,4 @@
-// Arguments of the fused norm + dropout + LeakyReLU kernels and their validation, shared by the streaming kernels (normact.hip) and
+// Arguments of the fused norm + dropout + LeakyReLU / PReLU kernels and their validation, shared by the streaming kernels (normact.hip) and
 // the one-workgroup-per-channel-piece kernels of small tensors (normact_small.hip), with the per-element backward both use.
 #pragma once
 #include "elementwise_common.h"
@@ -28,6 +28,9 @@ struct NormActArgs {
   // forward, optional: MaxPool3d(2) of a in the pass that writes it: pool_y[o][ch] = max over the window, pool_widx = the window
   // positions (as mi355_maxpool2_fwd_idx), extents pd x ph x pw (even)
   char* pool_y; int ldpy; uint8_t* pool_widx;
+  // PReLU: the trained slope in device memory (null: `slope`), read once per kernel by act_slope(); backward, the reducing kernels'
+  // PRELU instantiations: scratch for the partial sums of the slope gradient (streaming: f32 [groups * blocks][c], small: f64 [groups][c])
+  const float* alpha; void* dalpha_part;
 };
 
 constexpr int kImplicitMaxC = 64;     // channels of the implicit 1x1x1 data gradient's LDS weight table (normact.hip: fill_implicit_w)
@@ -45,10 +48,13 @@ __device__ __forceinline__ void load_bwd_const(const NormActArgs& q, int g, int 
     k.be[j] = (q.beta && ch < q.n_affine) ? q.beta[ch] : 0.f;
   }
 }
-// g = da * dropout * lrelu'(pre);  xhat = (z - mean) * rstd  (xhat = z when there is no norm)
+// the negative slope of this launch: uniform and loop-invariant, read before the row loop
+__device__ __forceinline__ float act_slope(const NormActArgs& q) { return q.alpha ? q.alpha[0] : q.slope; }
+// g = da * dropout * lrelu'(pre);  xhat = (z - mean) * rstd  (xhat = z when there is no norm);
+// aterm = this element's share of the slope gradient: [u <= 0] da u with u = Dropout(pre) (dead code where it is not summed)
 template <bool DROP>
-__device__ __forceinline__ void bwd_elem(const NormActArgs& q, bool keep, float mu, float rs, float ga,
-                                         float be, float zv, float dav, float& gout, float& xhat) {
+__device__ __forceinline__ void bwd_elem(const NormActArgs& q, float slope, bool keep, float mu, float rs, float ga,
+                                         float be, float zv, float dav, float& gout, float& xhat, float& aterm) {
   xhat = (zv - mu) * rs;
   float pre = xhat * ga + be;
   float gv = dav;
@@ -56,7 +62,30 @@ __device__ __forceinline__ void bwd_elem(const NormActArgs& q, bool keep, float 
     pre = keep ? pre : 0.f;
     gv = keep ? gv * q.drop_scale : 0.f;
   }
-  gout = pre > 0.f ? gv : gv * q.slope;
+  gout = pre > 0.f ? gv : gv * slope;
+  aterm = pre > 0.f ? 0.f : gv * pre;
+}
+template <bool DROP>
+__device__ __forceinline__ void bwd_elem(const NormActArgs& q, float slope, bool keep, float mu, float rs, float ga,
+                                         float be, float zv, float dav, float& gout, float& xhat) {
+  float aterm;
+  bwd_elem<DROP>(q, slope, keep, mu, rs, ga, be, zv, dav, gout, xhat, aterm);
+}
+
+// The slope gradient's last step (PReLU nodes only): n f64 partial sums -> one f32 scalar, written or accumulated.  ONE workgroup;
+// thread t adds src[t], src[t + 256], ... and the 256 totals are folded in a fixed tree: the same bits in every run.
+__global__ __launch_bounds__(256) void slope_grad_sum_kernel(const double* __restrict__ src, int n, float* __restrict__ out,
+                                                             int accumulate) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += src[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = accumulate ? out[0] + (float)red[0] : (float)red[0];
 }
 
 static int fill_normact(const mi355_normact_desc* d, NormActArgs* q, const char* who) {
@@ -70,6 +99,8 @@ static int fill_normact(const mi355_normact_desc* d, NormActArgs* q, const char*
   q->c = d->c; q->rows_per_group = d->rows_per_group; q->groups = d->groups;
   q->mean = d->mean; q->rstd = d->rstd; q->gamma = d->gamma; q->beta = d->beta;
   q->slope = d->slope;
+  q->alpha = d->alpha; q->dalpha_part = d->dalpha_part;
+  MI355_REQUIRE(!d->dalpha || (d->alpha && d->dalpha_part && d->mean), "%s: the slope gradient needs alpha, dalpha_part and a norm", who);
   q->thr16 = d->drop_p > 0.f ? (unsigned)(d->drop_p * 65536.f + 0.5f) : 0u;
   q->drop_scale = d->drop_p > 0.f ? 1.f / (1.f - d->drop_p) : 1.f;
   q->seed = d->seed;

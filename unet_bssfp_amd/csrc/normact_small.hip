@@ -54,6 +54,7 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_fwd_kernel(const 
   const NormActArgs& q = p.q;
   const int ch0 = blockIdx.x * EPV;
   const unsigned long long seed = DROP ? eff_seed(q.seed, q.seed_ptr) : 0ull;
+  const float slope = act_slope(q);
   float ga[EPV], be[EPV];
 #pragma unroll
   for (int j = 0; j < EPV; ++j) {
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_fwd_kernel(const 
         for (int j = 0; j < EPV; ++j) {
           float t2 = v.f[j] * sc[j] + sh[j];
           if constexpr (DROP) t2 = (keep >> j) & 1u ? t2 * q.drop_scale : 0.f;
-          v.f[j] = t2 > 0.f ? t2 : t2 * q.slope;
+          v.f[j] = t2 > 0.f ? t2 : t2 * slope;
         }
         if (q.s2d_a.d) {
           long long srow; int blk, border;
@@ -148,13 +149,16 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_fwd_kernel(const 
   }
 }
 
-template <typename T, bool DROP>
+// PRELU: a third sum, the slope gradient's share, per group and channel into q.dalpha_part ([groups][c] doubles); the host's
+// slope_grad_sum_kernel launch adds them
+template <typename T, bool DROP, bool PRELU = false>
 __global__ __launch_bounds__(kSmallThreads) void normact_small_bwd_kernel(const NormSmallArgs p) {
   constexpr int EPV = Elem<T>::kPer16B;
   __shared__ double red[kSmallWaves * EPV];
   const NormActArgs& q = p.q;
   const int ch0 = blockIdx.x * EPV;
   const unsigned long long seed = DROP ? eff_seed(q.seed, q.seed_ptr) : 0ull;
+  const float slope = act_slope(q);
   const double inv = 1.0 / (double)q.rows_per_group;
   double tg[EPV], tb[EPV];
 #pragma unroll
@@ -168,10 +172,10 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_bwd_kernel(const 
       if (q.s2d_da.d) return *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(q.da) + s2d_offset(q.s2d_da, (long long)g * q.rows_per_group + row, q.ldda) + ch0);
       return *reinterpret_cast<const uint4*>(db + row * q.ldda);
     };
-    float s0[EPV], s1[EPV];
+    float s0[EPV], s1[EPV], s2[EPV];
 #pragma unroll
-    for (int j = 0; j < EPV; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
-    constexpr int U = 2;                                   // (z and da rows in flight per thread: see the forward kernel)
+    for (int j = 0; j < EPV; ++j) { s0[j] = 0.f; s1[j] = 0.f; s2[j] = 0.f; }
+    constexpr int U = 2;                                 // (z and da rows in flight per thread: see the forward kernel)
     for (long long row0 = threadIdx.x; row0 < q.rows_per_group; row0 += kSmallThreads * U) {
       uint4 zr[U], dr[U];                                  // (packed while in flight)
 #pragma unroll
@@ -186,11 +190,21 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_bwd_kernel(const 
         if constexpr (DROP) keep = drop_keep_mask<EPV>(seed, ((unsigned long long)g * q.rows_per_group + row) * q.c + ch0, q.thr16);
 #pragma unroll
         for (int j = 0; j < EPV; ++j) {
-          float gv, xh;
-          bwd_elem<DROP>(q, (keep >> j) & 1u, k.mu[j], k.rs[j], k.ga[j], k.be[j], zv.f[j], dv.f[j], gv, xh);
+          float gv, xh, at;
+          bwd_elem<DROP>(q, slope, (keep >> j) & 1u, k.mu[j], k.rs[j], k.ga[j], k.be[j], zv.f[j], dv.f[j], gv, xh, at);
           s0[j] += gv;
           s1[j] += gv * xh;
+          if constexpr (PRELU) s2[j] += at;
         }
+      }
+    }
+    if constexpr (PRELU) {                 // (first, and written at once: its totals are live next to nothing else)
+      double t2[EPV];
+      block_sum_vec<EPV>(s2, t2, red);
+      if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < EPV; ++j)      // (padded channels: u = 0, but their da is whatever the producer left)
+          reinterpret_cast<double*>(q.dalpha_part)[(long long)g * q.c + ch0 + j] = ch0 + j < q.n_affine ? t2[j] : 0.0;
       }
     }
     double t0[EPV], t1[EPV];
@@ -221,7 +235,7 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_bwd_kernel(const 
 #pragma unroll
         for (int j = 0; j < EPV; ++j) {
           float gv, xh;
-          bwd_elem<DROP>(q, (keep >> j) & 1u, k.mu[j], k.rs[j], k.ga[j], k.be[j], zv.f[j], dv.f[j], gv, xh);
+          bwd_elem<DROP>(q, slope, (keep >> j) & 1u, k.mu[j], k.rs[j], k.ga[j], k.be[j], zv.f[j], dv.f[j], gv, xh);
           zv.f[j] = kk[j] * (gv - m0[j] - xh * m1[j]);
         }
         zv.store(ob + row * q.lddz);
@@ -290,6 +304,7 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_res_fwd_kernel(co
   const NormActArgs& q = p.q;
   const int ch0 = blockIdx.x * EPV;
   const unsigned long long seed = DROP ? eff_seed(q.seed, q.seed_ptr) : 0ull;
+  const float slope = act_slope(q);
   float ga[EPV], be[EPV];
 #pragma unroll
   for (int j = 0; j < EPV; ++j) {
@@ -376,7 +391,7 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_res_fwd_kernel(co
         for (int j = 0; j < EPV; ++j) {
           float t2 = v.f[j] * sc[j] + sh[j];
           if constexpr (DROP) t2 = (keep >> j) & 1u ? t2 * q.drop_scale : 0.f;
-          v.f[j] = t2 > 0.f ? t2 : t2 * q.slope;
+          v.f[j] = t2 > 0.f ? t2 : t2 * slope;
         }
         if (q.s2d_a.d) {
           long long srow; int blk, border;
@@ -400,7 +415,8 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_res_bwd_kernel(co
   const unsigned long long seed = DROP ? eff_seed(q.seed, q.seed_ptr) : 0ull;
   const double inv = 1.0 / (double)q.rows_per_group;
   const int rows = (int)q.rows_per_group;
-  constexpr int NST = S > 1 ? 3 : 0;                       // S = 8: the last 3 da rows wait in LDS between the passes (each thread its
+  const float slope = act_slope(q);
+  constexpr int NST = S > 1 ? 3 : 0;                      // S = 8: the last 3 da rows wait in LDS between the passes (each thread its
   __shared__ uint4 stash[NST ? NST * kSmallThreads : 1];   //  own 16-byte slots, conflict-free; as registers next to z they spilled 13 - 70)
   __shared__ double tot[kSmallResMaxGroups * 2 * EPV];     // per group (sum g | sum g * xhat), written by thread 0: the sums over the
                                                            //  groups are formed at the end (as 32 registers of every thread they spilled)
@@ -442,7 +458,7 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_res_bwd_kernel(co
 #pragma unroll
         for (int j = 0; j < EPV; ++j) {
           float gv, xh;
-          bwd_elem<DROP>(q, (keep >> j) & 1u, k[c].mu[j], k[c].rs[j], k[c].ga[j], k[c].be[j], zv.f[j], dv.f[j], gv, xh);
+          bwd_elem<DROP>(q, slope, (keep >> j) & 1u, k[c].mu[j], k[c].rs[j], k[c].ga[j], k[c].be[j], zv.f[j], dv.f[j], gv, xh);
           s[(2 * c) * EPV + j] += gv;
           s[(2 * c + 1) * EPV + j] += gv * xh;
         }
@@ -481,7 +497,7 @@ __global__ __launch_bounds__(kSmallThreads) void normact_small_res_bwd_kernel(co
 #pragma unroll
         for (int j = 0; j < EPV; ++j) {
           float gv, xh;
-          bwd_elem<DROP>(q, (keep >> j) & 1u, k[c].mu[j], k[c].rs[j], k[c].ga[j], k[c].be[j], zv.f[j], dv.f[j], gv, xh);
+          bwd_elem<DROP>(q, slope, (keep >> j) & 1u, k[c].mu[j], k[c].rs[j], k[c].ga[j], k[c].be[j], zv.f[j], dv.f[j], gv, xh);
           zv.f[j] = kk[j] * (gv - m0[j] - xh * m1[j]);
         }
         zv.store(ob + row * q.lddz);
@@ -566,6 +582,14 @@ int mi355_normact_small_bwd(const mi355_normact_small_desc* d, void* stream) {
   p.dgamma = d->dgamma; p.dbeta = d->dbeta; p.accumulate = d->accumulate;
   const int epv = d->base.dtype == MI355_DT_F32 ? 4 : 8;
   dim3 grid(d->base.c / epv);
+  if (d->base.dalpha) {
+    // PReLU with a slope gradient to form: the plain kernel with a third sum (the register-resident forms below sit at their register
+    // limit -- see the notes on NST and GC8 -- and were not given one more value per channel and group), then the sum over groups and channels
+    for_dtype_drop(d->base.dtype, p.q.thr16, [&](auto t, auto drop) { normact_small_bwd_kernel<decltype(t), drop, true><<<grid, dim3(kSmallThreads), 0, (hipStream_t)stream>>>(p); });
+    slope_grad_sum_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(reinterpret_cast<const double*>(d->base.dalpha_part),
+                                                                          p.q.groups * p.q.c, d->base.dalpha, d->accumulate);
+    return mi355_check_launch("normact_small_bwd");
+  }
   if (p.q.rows_per_group <= 8ll * kSmallThreads && p.q.groups <= kSmallResMaxGroups) {       // register-resident form: one load latency per chunk of groups
     const int s_slots = p.q.rows_per_group <= kSmallThreads ? 1 : 8, chunk = p.q.groups % 2 == 0 ? 2 : 1;
     // scratch for the per-group sums given (base.part: groups x 2 x c doubles): the chunks of groups are independent workgroups and the

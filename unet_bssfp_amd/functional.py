@@ -1102,9 +1102,12 @@ class UpCatConvFn(Function):
 
 # ====================================================================================== norm + act
 class NormCfg:
-    def __init__(self, kind, channels, eps=1e-5, momentum=0.1, slope=1.0, p=0.0):
-        assert kind in ("instance", "batch", "none")
+    def __init__(self, kind, channels, eps=1e-5, momentum=0.1, slope=1.0, p=0.0, act="leakyrelu"):
+        """act: "leakyrelu" (``slope`` by value; 0 is ReLU, 1 the identity) or "prelu" (the slope is a trained parameter handed
+        to NormActFn as ``alpha``; ``slope`` is not used)."""
+        assert kind in ("instance", "batch", "none") and act in ("leakyrelu", "prelu")
         self.kind, self.channels, self.eps, self.momentum, self.slope, self.p = kind, channels, eps, momentum, slope, p
+        self.act = act
 
 
 class DropoutState:
@@ -1148,16 +1151,17 @@ def begin_step(device):
     Fp8Scales.advance(device)
 
 
-NORMACT_INPUTS = 17         # NormActFn.forward's arguments after ctx: its backward returns one entry for each
+NORMACT_INPUTS = 18         # NormActFn.forward's arguments after ctx: its backward returns one entry for each
 
 
 class NormActFn(Function):
-    """a = LeakyReLU(Dropout(Norm(z)))  -- MONAI ADN "NDA" / BatchNorm3d + LeakyReLU."""
+    """a = LeakyReLU(Dropout(Norm(z)))  -- MONAI ADN "NDA" / BatchNorm3d + LeakyReLU; with cfg.act == "prelu" a = PReLU(...) and
+    ``alpha`` (the last input, f32[1]) is its trained slope: read on the device by every launch, its gradient returned."""
 
     @staticmethod
     def forward(ctx, z, part, gamma, beta, conv_bias, cfg: NormCfg, training, running_mean, running_var,
                 s2d_out: bool = False, batches_tracked=None, small: bool = False, bn_groups: int = 1,
-                emit8=None, emit8_bwd=None, final=None, pool_after: bool = False):
+                emit8=None, emit8_bwd=None, final=None, pool_after: bool = False, alpha=None):
         """bn_groups > 1: BatchNorm statistics per consecutive sample group (two forward calls of the discriminator stacked
         along the batch: each group is normalised with its own batch statistics, the running statistics receive the groups'
         momentum updates in order -- exactly what two separate calls do)."""
@@ -1166,6 +1170,8 @@ class NormActFn(Function):
         z = ops.as_act(z)
         n, d, h, w, c = z.shape
         rows = n * d * h * w
+        if (cfg.act == "prelu") != (alpha is not None) or (alpha is not None and cfg.kind == "none"):
+            raise ValueError("NormActFn: a PReLU node takes its slope as `alpha` (and a norm); a LeakyReLU node takes none")
         # statistics of the batch itself (instance norm; BatchNorm in training mode or without running statistics)?  In eval
         # mode BatchNorm normalises every sample with the SAME running statistics: one (1, c) mean / rstd row, one group --
         # whatever bn_groups says (a stacked forward_pair on a model in .eval(): ADVICE r3)
@@ -1206,18 +1212,19 @@ class NormActFn(Function):
         p = cfg.p if training else 0.0
         seed = DropoutState.next_salt() if p > 0.0 else 0
         seed_t = DropoutState.base(z.device) if p > 0.0 else None
+        ap = alpha.detach() if alpha is not None else None       # (a pointer for the kernels: never read on the host)
         if small:
             # small tensor (low U-Net levels, last PatchGAN blocks)
             out = _new_s2d(ops.s2d_shape(n, d, h, w, c), z.dtype, z.device) if s2d_out else None
             a, mean, rstd = ops.normact_small_fwd(z, groups, gp, bp, cfg.eps, cfg.slope, p, seed, seed_t,
                                                   running_mean if upd else None, running_var if upd else None, cfg.momentum,
-                                                  batches_tracked if upd else None, out=out, s2d=s2d_out)
+                                                  batches_tracked if upd else None, out=out, s2d=s2d_out, alpha=ap)
         elif s2d_out:
             out = _new_s2d(ops.s2d_shape(n, d, h, w, c), z.dtype, z.device)
-            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, out=out, s2d=True, seed_t=seed_t)
+            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, out=out, s2d=True, seed_t=seed_t, alpha=ap)
         elif emit8 is not None:
             a8 = torch.empty(z.shape, dtype=torch.uint8, device=z.device)
-            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t, q8=(a8, emit8.use, emit8.next))
+            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t, q8=(a8, emit8.use, emit8.next), alpha=ap)
             emit8.touched = True
             Fp8Side.put(a, a8)
         elif final is not None and z.dtype == torch.bfloat16 and c == 32:
@@ -1226,27 +1233,28 @@ class NormActFn(Function):
             fw, fb, skip_a = final               # (skip_a is the CALLER's `not torch.is_grad_enabled()`: in here grad mode is always off)
             y = ops.new_act(n, d, h, w, round_up(fw.shape[0], 16), z.dtype, z.device)
             a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t,
-                                final=(fw.detach(), fb.detach() if fb is not None else None, y), skip_a=skip_a)
+                                final=(fw.detach(), fb.detach() if fb is not None else None, y), skip_a=skip_a, alpha=ap)
             FusedFinal.put(a, y, fw, fw._version)
         elif (pool_after and PoolSide.enabled and not s2d_out and emit8 is None and d % 2 == 0 and h % 2 == 0 and w % 2 == 0
               and (rows // groups) % (d * h * w) == 0):
             # the activation's only consumer is SkipPoolFn (nn.Down.forward_skip): its MaxPool3d(2) in this launch (PoolSide)
-            a, py, pidx = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t, pool=True)
+            a, py, pidx = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t, pool=True, alpha=ap)
             PoolSide.put(a, py, pidx)
         else:
-            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t)
+            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t, alpha=ap)
         ctx.small = small
         ctx.s2d_out = s2d_out
         ctx.seed_t = seed_t
         ctx.affine_params = (gamma, beta)
-        ctx.save_for_backward(z, mean, rstd, gp, bp)
+        ctx.alpha_param = alpha
+        ctx.save_for_backward(z, mean, rstd, gp, bp, ap)
         ctx.meta = (groups, cfg.slope, p, seed, batch_stats, gamma.numel() if gamma is not None else 0)
         return a
 
     @staticmethod
     @once_differentiable
     def backward(ctx, da):
-        z, mean, rstd, gp, bp = ctx.saved_tensors
+        z, mean, rstd, gp, bp, ap = ctx.saved_tensors
         groups, slope, p, seed, batch_stats, nch = ctx.meta
         da = ops.as_act(da)
         lazy = LazyDx.take(da)                  # (dz, W) of the 1x1x1 convolution that consumed a: da is formed on the fly
@@ -1264,12 +1272,20 @@ class NormActFn(Function):
         need_g, need_b = ctx.needs_input_grad[2:4]
         want_affine = need_g or need_b
         gamma_p, beta_p = ctx.affine_params
-        kw = dict(s2d=ctx.s2d_out, seed_t=ctx.seed_t)
+        kw = dict(s2d=ctx.s2d_out, seed_t=ctx.seed_t, alpha=ap)
         sink = sink_of(gamma_p) if (need_g and need_b and mean is not None and sink_of(beta_p) is sink_of(gamma_p)) else None
         if sink is not None:
             # both affine gradients straight into the parameters' .grad storage (gradsink.py)
             _, dg_t, acc, _ = _grad_target(gamma_p)
             kw.update(affine_into=(dg_t, sink_grad(beta_p)), accumulate=acc)
+        # PReLU: the slope's gradient comes out of the same launches, written (or accumulated) where the parameter's gradient lives;
+        # the launches share one `accumulate` with the affine gradients -- where the two differ it goes through a scalar of its own
+        alpha_p, asink, da_t, da_tmp = ctx.alpha_param, None, None, None
+        if alpha_p is not None and ctx.needs_input_grad[NORMACT_INPUTS - 1]:
+            asink, da_t, a_acc, _ = _grad_target(alpha_p)
+            if a_acc != bool(kw.get("accumulate", False)):
+                da_tmp = torch.zeros_like(da_t)
+            kw.update(dalpha=da_t if da_tmp is None else da_tmp)
         if ctx.small:
             dz, dgamma, dbeta = ops.normact_small_bwd(z, da, groups, mean, rstd, gp, bp, slope, p, seed, batch_stats,
                                                       want_affine=want_affine, **kw)
@@ -1283,7 +1299,12 @@ class NormActFn(Function):
                 Fp8Side.put(dz, q8[0])
         dg = _grad_done(sink, gamma_p, dgamma[:nch].contiguous() if (dgamma is not None and need_g) else None)
         dbt = _grad_done(sink, beta_p, dbeta[:nch].contiguous() if (dbeta is not None and need_b) else None)
-        return (dz, None, dg, dbt) + (None,) * (NORMACT_INPUTS - 4)
+        dal = None
+        if da_t is not None:
+            if da_tmp is not None:
+                da_t.add_(da_tmp) if a_acc else da_t.copy_(da_tmp)
+            dal = _grad_done(asink, alpha_p, da_t)
+        return (dz, None, dg, dbt) + (None,) * (NORMACT_INPUTS - 5) + (dal,)
 
 
 # ====================================================================================== pool / loss

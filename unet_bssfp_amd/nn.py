@@ -55,6 +55,8 @@ def set_compute_dtype(module: nn.Module, dtype: torch.dtype) -> nn.Module:
     fp8 = dtype == FP8
     if fp8:
         dtype = torch.bfloat16
+        if any(isinstance(m, _ADN) and hasattr(m, "A") for m in module.modules()):
+            raise NotImplementedError("e4m3 operands with a PReLU network: not verified, use bf16")
     assert dtype in (torch.float32, torch.bfloat16)
     for m in module.modules():
         if isinstance(m, _Mi355Module):
@@ -349,21 +351,46 @@ class Discriminator(_Mi355Module):
 
 # ------------------------------------------------------------------------------------------
 # monai.networks.nets.BasicUNet (module/parameter names follow MONAI's state_dict)
+def parse_act(act):
+    """MONAI's ``act`` argument -- a name or (name, kwargs), the name matched without regard to case -> (kind, slope, init):
+    ("leakyrelu", negative slope, None) for "relu" (slope 0) and "leakyrelu" (torch's default 0.01; ``inplace`` means nothing
+    here), ("prelu", None, initial slope) for "prelu" with ONE trained slope (torch's default 0.25)."""
+    name, kw = (act[0], dict(act[1]) if len(act) > 1 else {}) if isinstance(act, (tuple, list)) else (act, {})
+    name = str(name).lower()
+    if name == "relu":
+        return "leakyrelu", 0.0, None
+    if name == "leakyrelu":
+        return "leakyrelu", float(kw.get("negative_slope", 0.01)), None
+    if name == "prelu":
+        if int(kw.get("num_parameters", 1)) != 1:
+            raise NotImplementedError("PReLU with one slope per channel (num_parameters != 1) is not implemented")
+        return "prelu", None, float(kw.get("init", 0.25))
+    raise NotImplementedError(f"act={act!r}: only ReLU, LeakyReLU and PReLU are implemented")
+
+
 class _ADN(nn.Module):
-    def __init__(self, channels):
+    def __init__(self, channels, prelu_init: Optional[float] = None):
         super().__init__()
         self.N = _NormParams(channels, batch=False)
+        if prelu_init is not None:
+            # torch.nn.PReLU as the parameter holder (A.weight, f32 (1,), after N as in MONAI's ADN; draws no random numbers);
+            # the arithmetic is the fused kernels'
+            self.A = nn.PReLU(num_parameters=1, init=prelu_init)
 
 
 class Convolution(_Mi355Module):
     """MONAI Convolution(k3, s1, p1, adn_ordering="NDA"): Conv3d -> InstanceNorm3d(affine) ->
-    Dropout(p) -> LeakyReLU(0.1), fused as conv(+statistics) -> finalize -> one apply pass."""
+    Dropout(p) -> LeakyReLU(0.1), fused as conv(+statistics) -> finalize -> one apply pass.
+    act (see parse_act) replaces ``slope``: ReLU, LeakyReLU with any slope, or PReLU with a trained slope ``adn.A.weight``."""
 
-    def __init__(self, cin, cout, dropout, slope=0.1, eps=1e-5):
+    def __init__(self, cin, cout, dropout, slope=0.1, eps=1e-5, act=None):
         super().__init__()
+        kind, init = "leakyrelu", None
+        if act is not None:
+            kind, slope, init = parse_act(act)
         self.conv = Conv3d(cin, cout, 3, 1, 1, bias=True)
-        self.adn = _ADN(cout)
-        self.cfg = Fn.NormCfg("instance", cout, eps=eps, slope=slope, p=float(dropout or 0.0))
+        self.adn = _ADN(cout, init)
+        self.cfg = Fn.NormCfg("instance", cout, eps=eps, slope=slope, p=float(dropout or 0.0), act=kind)
 
     def forward_act(self, x0, x1=None, feeds: Optional[Conv3d] = None, up_from=None, final: Optional[Conv3d] = None,
                     pool_after: bool = False):
@@ -399,14 +426,15 @@ class Convolution(_Mi355Module):
             # `final` is the 1x1x1 convolution that is this block's only consumer: evaluated by the norm + act launch itself
             fin = (final.weight, final.bias, not torch.is_grad_enabled())
         return Fn.NormActFn.apply(z, part if not small else None, self.adn.N.weight, self.adn.N.bias, shift, self.cfg,
-                                  self.training, None, None, False, None, small, 1, emit8, emit8_bwd, fin, pool_after)
+                                  self.training, None, None, False, None, small, 1, emit8, emit8_bwd, fin, pool_after,
+                                  self.adn.A.weight if self.cfg.act == "prelu" else None)
 
 
 class TwoConv(_Mi355Module):
-    def __init__(self, cin, cout, dropout):
+    def __init__(self, cin, cout, dropout, act=None):
         super().__init__()
-        self.conv_0 = Convolution(cin, cout, dropout)
-        self.conv_1 = Convolution(cout, cout, dropout)
+        self.conv_0 = Convolution(cin, cout, dropout, act=act)
+        self.conv_1 = Convolution(cout, cout, dropout, act=act)
 
     def forward_act(self, x0, x1=None, up_from=None, final=None, pool_after=False):
         return self.conv_1.forward_act(self.conv_0.forward_act(x0, x1, feeds=self.conv_1.conv, up_from=up_from), final=final,
@@ -414,9 +442,9 @@ class TwoConv(_Mi355Module):
 
 
 class Down(_Mi355Module):
-    def __init__(self, cin, cout, dropout):
+    def __init__(self, cin, cout, dropout, act=None):
         super().__init__()
-        self.convs = TwoConv(cin, cout, dropout)
+        self.convs = TwoConv(cin, cout, dropout, act)
 
     def forward_act(self, x):
         return self.convs.forward_act(Fn.MaxPoolFn.apply(x))
@@ -435,11 +463,11 @@ class _UpSample(nn.Module):
 
 
 class UpCat(_Mi355Module):
-    def __init__(self, cin, ccat, cout, dropout, halves=True):
+    def __init__(self, cin, ccat, cout, dropout, halves=True, act=None):
         super().__init__()
         cup = cin // 2 if halves else cin
         self.upsample = _UpSample(cin, cup)
-        self.convs = TwoConv(ccat + cup, cout, dropout)
+        self.convs = TwoConv(ccat + cup, cout, dropout, act)
 
     fuse_up_branch = True      # bf16, even extents: ConvTranspose3d + concat + Conv3d without the up-sampled tensor (Fn.UpCatConvFn)
 
@@ -487,23 +515,23 @@ class BasicUNet(_Mi355Module):
         rng_state = torch.get_rng_state() if spatial_dims == 2 else None
         if upsample != "deconv" or not bias:
             raise NotImplementedError("only upsample='deconv', bias=True (the reference's configuration)")
-        act_name = act[0] if isinstance(act, (tuple, list)) else act
         norm_name = norm[0] if isinstance(norm, (tuple, list)) else norm
-        if str(act_name).lower() != "leakyrelu" or str(norm_name).lower() != "instance":
-            raise NotImplementedError("only act=LeakyReLU / norm=instance (MONAI defaults used by the reference)")
+        if str(norm_name).lower() != "instance":
+            raise NotImplementedError("only norm=instance (the MONAI default used by the reference)")
+        parse_act(act)                  # (ReLU, LeakyReLU, PReLU with one slope: anything else raises NotImplementedError here)
         f = tuple(features)
         if len(f) != 6:
             raise ValueError("features must have 6 entries")
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.conv_0 = TwoConv(in_channels, f[0], dropout)
-        self.down_1 = Down(f[0], f[1], dropout)
-        self.down_2 = Down(f[1], f[2], dropout)
-        self.down_3 = Down(f[2], f[3], dropout)
-        self.down_4 = Down(f[3], f[4], dropout)
-        self.upcat_4 = UpCat(f[4], f[3], f[3], dropout)
-        self.upcat_3 = UpCat(f[3], f[2], f[2], dropout)
-        self.upcat_2 = UpCat(f[2], f[1], f[1], dropout)
-        self.upcat_1 = UpCat(f[1], f[0], f[5], dropout, halves=False)
+        self.conv_0 = TwoConv(in_channels, f[0], dropout, act)
+        self.down_1 = Down(f[0], f[1], dropout, act)
+        self.down_2 = Down(f[1], f[2], dropout, act)
+        self.down_3 = Down(f[2], f[3], dropout, act)
+        self.down_4 = Down(f[3], f[4], dropout, act)
+        self.upcat_4 = UpCat(f[4], f[3], f[3], dropout, act=act)
+        self.upcat_3 = UpCat(f[3], f[2], f[2], dropout, act=act)
+        self.upcat_2 = UpCat(f[2], f[1], f[1], dropout, act=act)
+        self.upcat_1 = UpCat(f[1], f[0], f[5], dropout, halves=False, act=act)
         self.final_conv = Conv3d(f[5], out_channels, kernel_size=1)
         if spatial_dims == 2:
             self._make_2d(rng_state)
@@ -608,12 +636,15 @@ def backward_stages(net: nn.Module, modality, frozen=()):
 class Generator(_Mi355Module):
     """src/model.py:15-39: modality head (1x1x1 DownSampleConv) -> BasicUNet(24 -> 6)."""
 
-    def __init__(self, input_modality, dropout=0.05, features=(32, 64, 128, 256, 512, 32)):
+    def __init__(self, input_modality, dropout=0.05, features=(32, 64, 128, 256, 512, 32), act=None):
+        """act: the U-Net's activation as BasicUNet takes it (None: MONAI's default LeakyReLU(0.1)); "PReLU" is the thesis's
+        choice (doc/thesis/03-methods.tex:760).  The modality heads keep their LeakyReLU(0.2)."""
         super().__init__()
         self.input_modality = input_modality
         dwi_tensor_input = DownSampleConv(6, 24, kernel=1, strides=1, padding=0)
         bssfp_input = DownSampleConv(24, 24, kernel=1, strides=1, padding=0)
-        unet = BasicUNet(spatial_dims=3, in_channels=24, out_channels=6, features=features, dropout=dropout)
+        kw = {} if act is None else {"act": act}
+        unet = BasicUNet(spatial_dims=3, in_channels=24, out_channels=6, features=features, dropout=dropout, **kw)
         self.blocks = nn.ModuleDict({"dwi-tensor": dwi_tensor_input, "pc-bssfp": bssfp_input,
                                      "bssfp": bssfp_input, "t1w": dwi_tensor_input, "unet": unet})
 

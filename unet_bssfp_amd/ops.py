@@ -581,8 +581,15 @@ def colsum_from_parts(part: torch.Tensor, offset: int, out: torch.Tensor, accumu
                                                       1 if accumulate else 0, _stream()), "colsum_from_parts")
 
 
-def _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t=None):
+def _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t=None, alpha=None):
+    """alpha (f32[1] on the device, or None): PReLU's trained slope -- the kernels read it through the pointer at launch time
+    and `slope` is not used (no host read: an optimiser updates it in place and a replayed hipGraph sees the update)."""
     d = _lib.NormActDesc()
+    if alpha is not None:
+        require_cuda(alpha)
+        if alpha.dtype != torch.float32 or alpha.numel() != 1:
+            raise ValueError(f"PReLU's slope must be one f32 value, got {tuple(alpha.shape)} {alpha.dtype}")
+        d.alpha = alpha.data_ptr()
     n, dd, h, w, c = z.shape
     rows = n * dd * h * w
     d.z, d.ldz, d.c = z.data_ptr(), act_ld(z), c
@@ -593,7 +600,7 @@ def _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_
             raise ValueError(f"norm statistics hold {t.numel()} values for {groups} group(s) x {c} channels")
     d.mean, d.rstd, d.gamma, d.beta = _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta)
     d.n_affine = gamma.numel() if gamma is not None else 0
-    d.slope, d.drop_p, d.seed = slope, drop_p, seed
+    d.slope, d.drop_p, d.seed = (0.0 if slope is None else slope), drop_p, seed
     d.seed_ptr = _ptr(seed_t)
     d.dtype = _DT[z.dtype]
     return d
@@ -620,18 +627,19 @@ def _set_q8(d, q8):
 
 
 def normact_fwd(z, groups, mean, rstd, gamma, beta, slope, drop_p=0.0, seed=0, out=None, s2d=False, seed_t=None, q8=None,
-                final=None, skip_a=False, pool=False):
+                final=None, skip_a=False, pool=False, alpha=None):
     """s2d=True: `out` is the space-to-depth tensor S(a) (s2d_shape) instead of a plain one; every slot of it is written.
     q8: also write the e4m3 copy of the result for the fp8 convolution that consumes it (see _set_q8).
     final=(w, bias, y): also evaluate the 1x1x1 convolution that consumes a -- y[..., k] = bf16(a @ bf16(w[k]) + bias[k]), w f32
     (k <= 8, cin[, 1, 1, 1]), y a bf16 NDHWC tensor on the same grid whose channels beyond k are zeroed; skip_a: a itself is not
     written (the returned tensor is uninitialised).
     pool=True: also MaxPool3d(2) of the result in the same pass -> (a, y, idx) as maxpool2_fwd(a, want_idx=True) (even extents,
-    plain layout, no q8 / final)."""
+    plain layout, no q8 / final).
+    alpha: PReLU's slope on the device instead of `slope` (see _normact_desc); every form above takes it."""
     require_cuda(z, mean, rstd, gamma, beta, out)
     if out is None:
         out = torch.empty(z.shape, dtype=z.dtype, device=z.device)
-    d = _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t)
+    d = _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t, alpha)
     d.a, d.lda = out.data_ptr(), act_ld(out)
     keep_final = None
     if final is not None:
@@ -668,7 +676,8 @@ def normact_fwd(z, groups, mean, rstd, gamma, beta, slope, drop_p=0.0, seed=0, o
 
 
 def normact_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, seed, batch_stats, want_affine_grads,
-                s2d=False, seed_t=None, affine_into=None, accumulate=False, q8=None, implicit=None, pool=None):
+                s2d=False, seed_t=None, affine_into=None, accumulate=False, q8=None, implicit=None, pool=None,
+                alpha=None, dalpha=None):
     """Returns (dz, dgamma, dbeta).  dgamma/dbeta are f32 [C] (None if there is no norm).
     s2d=True: `da` is a gradient in space-to-depth layout (the forward wrote S(a)).
     affine_into=(dgamma, dbeta): write (accumulate=True: add) the affine gradients into these caller-owned f32
@@ -676,12 +685,19 @@ def normact_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, seed, bat
     implicit=(gz, gw): `da` is not materialised (pass None): it is the data gradient of the 1x1x1 convolution that consumed a,
     da = bf16(gz[..., :k] @ gw) with gz the NDHWC gradient of that convolution's output and gw its f32 weights (k, cin[,1,1,1]).
     pool=(idx, dy): `da` is the gradient of a's skip-connection use only (or None): the activation was also consumed by MaxPool3d(2)
-    (idx from maxpool2_fwd(want_idx=True), dy the pooled tensor's gradient) and the kernels form maxpool2_bwd(..., add=da) per row."""
+    (idx from maxpool2_fwd(want_idx=True), dy the pooled tensor's gradient) and the kernels form maxpool2_bwd(..., add=da) per row.
+    alpha: PReLU's slope on the device (see _normact_desc).  dalpha (f32[1], with alpha and a norm): the slope's gradient is written
+    there (accumulate=True: added) by the reduce / finalize launches and one single-workgroup launch after them."""
     require_cuda(z, da)
     lib = _lib.load()
     n, dd, h, w, c = z.shape
     rows = n * dd * h * w
-    d = _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t)
+    d = _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t, alpha)
+    if dalpha is not None:
+        require_cuda(dalpha)
+        if alpha is None or mean is None:
+            raise ValueError("normact_bwd: a slope gradient needs the slope on the device (alpha) and a norm")
+        assert dalpha.dtype == torch.float32 and dalpha.numel() == 1
     keep_implicit = None
     if implicit is not None:
         gz, gw = implicit
@@ -715,22 +731,43 @@ def normact_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, seed, bat
     dgamma = dbeta = None
     keep = []
     after = _norm_probe("bwd", z, gamma)
-    if mean is not None and (batch_stats or want_affine_grads):
+    if mean is not None and (batch_stats or want_affine_grads or dalpha is not None):
         bpg = lib.mi355_channel_stats_blocks(rows // groups)
-        part = torch.empty((groups * bpg, 2, c), dtype=torch.float32, device=z.device)
+        # one buffer of rows of c floats: the partials [groups * bpg][2][c]; behind them, for a slope gradient, its partials
+        # [groups * bpg][c] and the per-channel totals (c doubles = 2 rows; the offset is a multiple of 16 bytes)
+        nparts = groups * bpg
+        nrows = 2 * nparts if dalpha is None else 3 * nparts + 2
+        buf = torch.empty((nrows, c), dtype=torch.float32, device=z.device)
+        part = buf[:2 * nparts]
         d.part, d.blocks_per_group = part.data_ptr(), bpg
+        if dalpha is not None:
+            apart, alpha_ch = buf[2 * nparts: 3 * nparts], buf[3 * nparts:]
+            d.dalpha, d.dalpha_part = dalpha.data_ptr(), apart.data_ptr()
         _lib.check(lib.mi355_normact_bwd_reduce(C.byref(d), _stream()), "normact_bwd_reduce")
         sums = torch.empty((groups, 2, c), dtype=torch.float32, device=z.device)
         if affine_into is not None:
             g_into, b_into = affine_into
             require_cuda(g_into, b_into)
             assert g_into.dtype == b_into.dtype == torch.float32 and g_into.numel() == b_into.numel() <= c
+        else:
+            dgamma = torch.empty((c,), dtype=torch.float32, device=z.device)
+            dbeta = torch.empty((c,), dtype=torch.float32, device=z.device)
+        if dalpha is not None:
+            if affine_into is None and accumulate:
+                raise ValueError("normact_bwd: accumulate goes with affine_into (fresh affine gradients have nothing to add to)")
+            # (n_affine: the real channels -- padded channels add nothing to the slope gradient, and their affine gradients
+            #  are not written)
+            g_t, b_t = (g_into, b_into) if affine_into is not None else (dgamma, dbeta)
+            n_aff = g_into.numel() if affine_into is not None else (d.n_affine or c)
+            _lib.check(lib.mi355_normact_bwd_finalize_prelu(part.data_ptr(), apart.data_ptr(), bpg, groups, c, sums.data_ptr(),
+                                                            g_t.data_ptr(), b_t.data_ptr(), n_aff, 1 if accumulate else 0,
+                                                            alpha_ch.data_ptr(), dalpha.data_ptr(), _stream()),
+                       "normact_bwd_finalize_prelu")
+        elif affine_into is not None:
             _lib.check(lib.mi355_normact_bwd_finalize_into(part.data_ptr(), bpg, groups, c, sums.data_ptr(),
                                                            g_into.data_ptr(), b_into.data_ptr(), g_into.numel(),
                                                            1 if accumulate else 0, _stream()), "normact_bwd_finalize")
         else:
-            dgamma = torch.empty((c,), dtype=torch.float32, device=z.device)
-            dbeta = torch.empty((c,), dtype=torch.float32, device=z.device)
             _lib.check(lib.mi355_normact_bwd_finalize(part.data_ptr(), bpg, groups, c, sums.data_ptr(),
                                                       dgamma.data_ptr(), dbeta.data_ptr(), _stream()),
                        "normact_bwd_finalize")
@@ -758,9 +795,9 @@ def norm_is_small(n: int, d: int, h: int, w: int, c: int, serial_groups: int = 1
 
 
 def normact_small_fwd(z, groups, gamma, beta, eps, slope, drop_p=0.0, seed=0, seed_t=None, running_mean=None,
-                      running_var=None, momentum=0.0, batches_tracked=None, out=None, s2d=False):
+                      running_var=None, momentum=0.0, batches_tracked=None, out=None, s2d=False, alpha=None):
     """Statistics + norm + dropout + LeakyReLU of a small tensor in ONE launch.  Returns (a, mean, rstd); BatchNorm running
-    statistics (given: training mode) are updated in place."""
+    statistics (given: training mode) are updated in place.  alpha: PReLU's slope on the device (see _normact_desc)."""
     require_cuda(z, gamma, beta, out, running_mean, running_var)
     n, dd, h, w, c = z.shape
     if out is None:
@@ -768,7 +805,7 @@ def normact_small_fwd(z, groups, gamma, beta, eps, slope, drop_p=0.0, seed=0, se
     mean = torch.empty((groups, c), dtype=torch.float32, device=z.device)
     rstd = torch.empty_like(mean)
     d = _lib.NormSmallDesc()
-    d.base = _normact_desc(z, groups, None, None, gamma, beta, slope, drop_p, seed, seed_t)
+    d.base = _normact_desc(z, groups, None, None, gamma, beta, slope, drop_p, seed, seed_t, alpha)
     d.base.a, d.base.lda = out.data_ptr(), act_ld(out)
     if s2d:
         d.base.s2d_a = 1
@@ -785,14 +822,25 @@ def normact_small_fwd(z, groups, gamma, beta, eps, slope, drop_p=0.0, seed=0, se
 
 
 def normact_small_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, seed, batch_stats, s2d=False, seed_t=None,
-                      affine_into=None, accumulate=False, want_affine=True, group_scratch=None):
+                      affine_into=None, accumulate=False, want_affine=True, group_scratch=None, alpha=None, dalpha=None):
     """Backward of the above in ONE launch: returns (dz, dgamma, dbeta) -- the affine gradients are None when written into
     ``affine_into`` (caller-owned f32 vectors of the real channel count) or not wanted.  ``group_scratch`` (None: for three or
-    more statistic groups): hand the kernel scratch for per-group sums, see below."""
+    more statistic groups): hand the kernel scratch for per-group sums, see below.
+    alpha: PReLU's slope on the device (see _normact_desc).  dalpha (f32[1], with alpha): the slope's gradient is written there
+    (accumulate=True: added) -- a third sum in the same launch (its plain form, not the register-resident one) plus one
+    single-workgroup launch over the per-group, per-channel totals."""
     require_cuda(z, da, mean, rstd)
     n, dd, h, w, c = z.shape
     d = _lib.NormSmallDesc()
-    d.base = _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t)
+    d.base = _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t, alpha)
+    if dalpha is not None:
+        require_cuda(dalpha)
+        if alpha is None:
+            raise ValueError("normact_small_bwd: a slope gradient needs the slope on the device (alpha)")
+        if accumulate and affine_into is None:
+            raise ValueError("normact_small_bwd: accumulate goes with affine_into (fresh affine gradients have nothing to add to)")
+        assert dalpha.dtype == torch.float32 and dalpha.numel() == 1
+        d.base.dalpha = dalpha.data_ptr()
     d.base.da, d.base.ldda = da.data_ptr(), act_ld(da)
     dz = torch.empty(z.shape, dtype=z.dtype, device=z.device)
     d.base.dz, d.base.lddz = dz.data_ptr(), act_ld(dz)
@@ -812,11 +860,15 @@ def normact_small_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, see
         dbeta = torch.zeros((c,), dtype=torch.float32, device=z.device)
         d.dgamma, d.dbeta, d.accumulate = dgamma.data_ptr(), dbeta.data_ptr(), 0
     # three or more statistic groups (the reference's batch of 8 patches): scratch for the per-group sums, so that the chunks of
-    # groups run as independent workgroups and a second tiny launch sums the affine gradients over the groups (same order, f64)
+    # groups run as independent workgroups and a second tiny launch sums the affine gradients over the groups (same order, f64).
+    # A slope gradient: the same scratch holds its per-group, per-channel totals ([groups][c] doubles, the first half) instead
     gpart = None
-    if (groups >= 3) if group_scratch is None else group_scratch:
+    if dalpha is not None or ((groups >= 3) if group_scratch is None else group_scratch):
         gpart = torch.empty((groups, 2, c), dtype=torch.float64, device=z.device)
-        d.base.part = gpart.data_ptr()
+        if dalpha is not None:
+            d.base.dalpha_part = gpart.data_ptr()
+        else:
+            d.base.part = gpart.data_ptr()
     after = _norm_probe("bwd", z, gamma)
     _lib.check(_lib.load().mi355_normact_small_bwd(C.byref(d), _stream()), "normact_small_bwd")
     if after is not None:
