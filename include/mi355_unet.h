@@ -377,6 +377,35 @@ typedef struct mi355_normact_small_desc {
 int mi355_normact_small_fwd(const mi355_normact_small_desc* d, void* stream);
 int mi355_normact_small_bwd(const mi355_normact_small_desc* d, void* stream);
 
+/* Tail of a ResNet input head (the thesis's input block, doc/thesis/03-methods.tex:763-764; MONAI ResidualUnit with ADN "NDA"):
+ * norm + ReLU of the last convolution's output z PLUS the residual branch of the block's input x, one launch (csrc/resunit.hip):
+ *   y[row][ch] = store( max(0, (z[row][ch] - mean[g][ch]) * rstd[g][ch] * gamma[ch] + beta[ch]) + r[row][ch] )   ch <  n_real
+ *   y[row][ch] = 0                                                                                                n_real <= ch < c
+ *   r[row][ch] = x[row][ch]                                        (identity: rw == NULL, rb == NULL, cx == n_real)
+ *   r[row][ch] = rb[ch] + sum_{ci < cx} x[row][ci] * W[ch][ci]     (projection: rw = f32 master weights [n_real][cx], rb [n_real] or NULL)
+ * z, y (rows of c channels, a multiple of 16) and x (rows that hold cx real channels first) are NDHWC activations of `dtype`
+ * (f32 or bf16) with row strides ldz, ldy, ldx; mean / rstd are [groups][c] as in mi355_normact_desc (from mi355_norm_finalize; one
+ * (1, c) row with groups = 1 for running statistics), gamma / beta [n_real] (NULL: 1 / 0).  Arithmetic is f32 with ONE rounding, at
+ * the store; the norm is evaluated as z * sc + sh with sc = gamma * rstd, sh = beta - mean * sc, as mi355_normact_fwd does; the
+ * projection starts at rb[ch] and adds the products in ascending ci (fused multiply-add).  In bf16 mode W = bf16(rw)
+ * (the rule of fy / gw above); in f32 mode the master weights as they are.  Every element of y is written, pad channels included
+ * (exact zeros, whatever z and x hold there).  Input channels >= cx of x are never used.  No dropout, no other activation.
+ * layout: 0 = plain NDHWC rows; anything else, c > 64, or a projection of more than 32 input channels returns
+ * MI355_ERR_UNSUPPORTED.  Per row the launch moves 2c + 2cxp + 2c bytes in bf16 (z, the padded x row, y) -- composed from
+ * mi355_normact_fwd, a 1x1x1 mi355_conv_fwd and an add it is three more streams of a full-resolution tensor.
+ * There is no backward entry: the gradients are mi355_normact_bwd_* on z with da = dy (they recompute the ReLU mask from z),
+ * mi355_conv_wgrad / a column sum for rw / rb, and dy itself (identity) or the 1x1x1 data gradient (projection) for x. */
+typedef struct mi355_restail_desc {
+  const void* z; int32_t ldz;
+  const void* x; int32_t ldx; int32_t cx;
+  void* y; int32_t ldy;
+  int32_t c, n_real; int64_t rows_per_group; int32_t groups;
+  const float* mean; const float* rstd; const float* gamma; const float* beta;
+  const float* rw; const float* rb;
+  int32_t dtype; int32_t layout;
+} mi355_restail_desc;
+int mi355_restail_fwd(const mi355_restail_desc* d, void* stream);
+
 /* per-channel sum over all rows (bias gradient of a conv without normalisation):
  * out[c] = sum_rows x[row][c] from channel_stats partials (parts x [2][c]) */
 int mi355_colsum_finalize(const float* part, int32_t parts, int32_t c, float* out, void* stream);

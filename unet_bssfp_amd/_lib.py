@@ -91,6 +91,13 @@ class NormSmallDesc(C.Structure):
                 ("dgamma", _vp), ("dbeta", _vp), ("accumulate", _i32)]
 
 
+class ResTailDesc(C.Structure):
+    _fields_ = [("z", _vp), ("ldz", _i32), ("x", _vp), ("ldx", _i32), ("cx", _i32), ("y", _vp), ("ldy", _i32),
+                ("c", _i32), ("n_real", _i32), ("rows_per_group", _i64), ("groups", _i32),
+                ("mean", _vp), ("rstd", _vp), ("gamma", _vp), ("beta", _vp), ("rw", _vp), ("rb", _vp),
+                ("dtype", _i32), ("layout", _i32)]
+
+
 _SIGNATURES = {
     "mi355_version": (C.c_int, []),
     "mi355_last_error": (C.c_char_p, []),
@@ -130,6 +137,7 @@ _SIGNATURES = {
     "mi355_normact_bwd_apply": (C.c_int, [C.POINTER(NormActDesc), _vp]),
     "mi355_normact_small_fwd": (C.c_int, [C.POINTER(NormSmallDesc), _vp]),
     "mi355_normact_small_bwd": (C.c_int, [C.POINTER(NormSmallDesc), _vp]),
+    "mi355_restail_fwd": (C.c_int, [C.POINTER(ResTailDesc), _vp]),
     "mi355_colsum_finalize": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "mi355_colsum_finalize_into": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "mi355_colsum_finalize_from": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),

@@ -13,7 +13,8 @@ The reference trains under ``pl.Trainer`` with ``ModelCheckpoint`` (src/train.py
     'hyper_parameters'  what ``save_hyperparameters`` recorded (src/model.py:149): input_modality, lr,
                         batch_size, perceptual_factor, recon_factor; a model in a training state (stages.py) adds
                         'training_state' (a plain string, ``'TrainingState.TRANSFER'``) and 'stage_lr' -- absent without
-                        a state, so such files are what they were
+                        a state, so such files are what they were; a model built with ``gen_head=`` / ``gen_act=`` adds
+                        'gen_head' (a string) / 'gen_act' (a string, or a [name, {kwargs}] list) -- absent when not set
     'epoch', 'global_step', 'pytorch-lightning_version', 'lr_schedulers', 'callbacks', 'loops'
 
 Files are read with ``torch.load(weights_only=True)`` only: nothing in the file is executed, and a
@@ -27,6 +28,7 @@ import torch
 
 LIGHTNING_VERSION = "2.2.1"          # requirements.txt:1 of the reference
 HPARAM_KEYS = ("input_modality", "lr", "batch_size", "perceptual_factor", "recon_factor")
+OPTIONAL_HPARAM_KEYS = ("gen_head", "gen_act")      # the generator's architecture (gan.bSSFPToDWITensorModel); written only when set
 _OWN_PREFIXES = ("gen.", "discr.")
 
 
@@ -52,6 +54,9 @@ def checkpoint_dict(model, epoch: int = 0, global_step: int = 0) -> Dict:
         dev = next(model.gen.parameters()).device
         extra["dropout_base"] = int(DropoutState.base(dev).item())
     hparams = {k: getattr(model, k) for k in HPARAM_KEYS}
+    for k in OPTIONAL_HPARAM_KEYS:
+        if getattr(model, k, None) is not None:
+            hparams[k] = _plain(getattr(model, k))
     if getattr(model, "training_state", None) is not None:
         hparams["training_state"] = str(model.training_state)
         hparams["stage_lr"] = float(model.stage_lr)
@@ -135,15 +140,18 @@ def load_from_checkpoint(path: str, device: Optional[str] = None, **overrides):
     hyper-parameters, then load weights and both optimizer states.  A stored training state (stages.py) is restored with
     its rate.  ``training_state=`` (a ``TrainingState``, its name, or ``None``) and ``input_modality=`` rebuild the model for
     the next stage instead: the weights are loaded, the state's rate is the table's unless ``stage_lr=`` is given, and the
-    optimisers start fresh whenever the state, or the modality inside a state, differs from the stored one."""
+    optimisers start fresh whenever the state, or the modality inside a state, differs from the stored one.  A stored ``gen_head`` /
+    ``gen_act`` rebuilds the generator it describes; ``gen_head=`` / ``gen_act=`` override them, ``gen=`` replaces them."""
     from .gan import bSSFPToDWITensorModel
     from .stages import parse_state
     stored = dict(torch.load(path, map_location="cpu", weights_only=True).get("hyper_parameters") or {})
-    hp = {k: v for k, v in stored.items() if k in HPARAM_KEYS}
+    hp = {k: v for k, v in stored.items() if k in HPARAM_KEYS + OPTIONAL_HPARAM_KEYS}
     stored_state = parse_state(stored.get("training_state"))
     state = parse_state(overrides.pop("training_state")) if "training_state" in overrides else stored_state
     same_stage = state is stored_state and overrides.get("input_modality", hp.get("input_modality")) == hp.get("input_modality")
     lr = overrides.pop("stage_lr", stored.get("stage_lr") if same_stage else None)
+    if overrides.get("gen") is not None:           # a generator handed over replaces the stored description of one
+        hp = {k: v for k, v in hp.items() if k not in OPTIONAL_HPARAM_KEYS}
     hp.update(overrides)
     if "input_modality" not in hp:
         raise KeyError(f"{path}: no 'input_modality' among the hyper-parameters; pass it explicitly")

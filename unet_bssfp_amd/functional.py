@@ -1307,6 +1307,96 @@ class NormActFn(Function):
         return (dz, None, dg, dbt) + (None,) * (NORMACT_INPUTS - 5) + (dal,)
 
 
+class ResTailFn(Function):
+    """y = ReLU(Norm(z)) + residual(x): the tail of nn.ResidualUnit (MONAI ResidualUnit, ADN "NDA", no activation after the sum) as
+    ONE launch (ops.restail_fwd) instead of a norm + act launch, a 1x1x1 convolution and an add.  z: the last convolution's
+    output, part: its fused statistics, x: the block's input; residual(x) = x when ``res_weight`` is None, else the 1x1x1
+    convolution (res_weight, res_bias), ``res_spec`` its ConvSpec.  cfg: NormCfg with slope 0, no dropout, batch or instance
+    statistics from the convolution's partials as in NormActFn (eval-mode BatchNorm: the running statistics as one (1, c) row).
+    Backward: the existing launches -- ops.normact_bwd on z with da = dy (it recomputes the ReLU mask from z), the streaming
+    1x1x1 weight gradient and a column sum for the residual convolution, and for x (when it needs one) dy itself or the 1x1x1
+    data gradient."""
+
+    @staticmethod
+    def forward(ctx, z, part, x, gamma, beta, conv_bias, res_weight, res_bias, res_spec: Optional[ConvSpec], cfg: NormCfg,
+                training, running_mean, running_var, batches_tracked=None):
+        z, x = ops.as_act(z), ops.as_act(x)
+        n, d, h, w, c = z.shape
+        rows = n * d * h * w
+        if cfg.kind == "none" or cfg.act != "leakyrelu" or cfg.slope != 0.0 or cfg.p != 0.0:
+            raise ValueError("ResTailFn: a norm followed by ReLU, without dropout")
+        use_batch = cfg.kind == "instance" or training or running_mean is None
+        groups = n if cfg.kind == "instance" else 1
+        if use_batch:
+            if rows // groups <= 1:
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
+            upd = cfg.kind == "batch" and training and running_mean is not None
+            if part is not None and part.numel() > 0:
+                assert part.shape[2] == c, "fused statistics need coutp == padded channels"
+                ppg, shift = part.shape[0] // groups, (conv_bias.detach() if conv_bias is not None else None)
+            else:
+                (part, ppg), shift = ops.channel_stats(z, groups), None
+            n_real = running_mean.numel() if upd else (shift.numel() if shift is not None else 0)
+            mean, rstd = ops.norm_finalize(part, ppg, groups, c, rows // groups, shift, cfg.eps, running_mean if upd else None,
+                                           running_var if upd else None, cfg.momentum, n_real=n_real,
+                                           batches_tracked=batches_tracked if upd else None)
+        else:
+            mean = _padded(running_mean, c).reshape(1, c)
+            rstd = torch.rsqrt(_padded(running_var, c, 1.0) + cfg.eps).reshape(1, c)
+        gp, bp = gamma.detach(), beta.detach()
+        rw = res_weight.detach() if res_weight is not None else None
+        rb = res_bias.detach() if res_bias is not None else None
+        cx = res_spec.cin if res_weight is not None else cfg.channels
+        y = ops.restail_fwd(z, x, groups, mean, rstd, gp, bp, cfg.channels, cx, rw, rb)
+        ctx.save_for_backward(z, x, mean, rstd, gp, bp)
+        ctx.params = (gamma, beta, res_weight, res_bias)
+        ctx.res_spec = res_spec
+        ctx.meta = (groups, use_batch, cfg.channels)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        z, x, mean, rstd, gp, bp = ctx.saved_tensors
+        gamma_p, beta_p, rw_p, rb_p = ctx.params
+        groups, batch_stats, nch = ctx.meta
+        spec: Optional[ConvSpec] = ctx.res_spec
+        dy = ops.as_act(dy)
+        n, d, h, w, c = z.shape
+        need_z, _, need_x, need_g, need_b, _, need_rw, need_rb = ctx.needs_input_grad[:8]
+        dz = dg = dbt = dx = drw = drb = None
+        if need_z or need_g or need_b:
+            # norm + ReLU: exactly NormActFn's launches with slope 0 and no dropout
+            kw = {}
+            sink = sink_of(gamma_p) if (need_g and need_b and sink_of(beta_p) is sink_of(gamma_p)) else None
+            if sink is not None:
+                _, dg_t, acc, _ = _grad_target(gamma_p)
+                kw.update(affine_into=(dg_t, sink_grad(beta_p)), accumulate=acc)
+            dz, dgamma, dbeta = ops.normact_bwd(z, dy, groups, mean, rstd, gp, bp, 0.0, 0.0, 0, batch_stats, need_g or need_b, **kw)
+            dg = _grad_done(sink, gamma_p, dgamma[:nch].contiguous() if (dgamma is not None and need_g) else None)
+            dbt = _grad_done(sink, beta_p, dbeta[:nch].contiguous() if (dbeta is not None and need_b) else None)
+        if rw_p is None:
+            dx = dy if need_x else None
+        else:
+            if need_x:
+                wp, coutp, _ = spec.w_dgrad_s1(rw_p, z.dtype, c)
+                dx = ops.new_act(n, d, h, w, x.shape[4], z.dtype, z.device)
+                ops.conv_fwd(dy, None, wp, coutp, None, 1, 1, (0, 0, 0), dx, (d, h, w), real=(spec.cout, spec.cin))
+            if need_rw:
+                wsink, dwt, acc, defer = _grad_target(rw_p, deferrable=True)
+                ops.conv_wgrad(x, None, dy, (d, h, w), 1, (0, 0, 0), 1, 1, (0, 0, 0), dwt, spec.cout, spec.cin, spec.cin, 1, (1, 1, 1),
+                               (0, 0, 0), (1, 1, 1), accumulate=acc, defer=defer)
+                drw = _grad_done(wsink, rw_p, dwt, defer)
+            if rb_p is not None and need_rb:
+                if sink_of(rb_p) is None:
+                    drb = ops.colsum(dy)[: spec.cout].contiguous()
+                else:
+                    bsink, dbt_, bacc, _ = _grad_target(rb_p)
+                    ops.colsum_into(dy, dbt_, accumulate=bacc)
+                    drb = _grad_done(bsink, rb_p, dbt_)
+        return dz, None, dx, dg, dbt, None, drw, drb, None, None, None, None, None, None
+
+
 # ====================================================================================== pool / loss
 class MaxPoolFn(Function):
     @staticmethod

@@ -45,12 +45,19 @@ class bSSFPToDWITensorModel(nn.Module):
                  gen: Optional[nn.Module] = None, discr: Optional[nn.Module] = None,
                  l1_fn: Optional[Callable] = None, optimizer_class=None,
                  extra_recon_terms: Optional[Dict[str, Callable]] = None, recon_divisor: Optional[int] = None,
-                 reference_quirks: bool = False, medicalnet: Optional[nn.Module] = None, fine_tune_lr: float = 1e-5):
+                 reference_quirks: bool = False, medicalnet: Optional[nn.Module] = None, fine_tune_lr: float = 1e-5,
+                 gen_head: Optional[str] = None, gen_act=None):
+        """gen_head / gen_act: when ``gen`` is not given, the generator is ``Generator(input_modality, head=gen_head or "conv",
+        act=gen_act)`` -- ``gen_head="resnet", gen_act="prelu"`` is the thesis's network.  Both are recorded among the checkpoint's
+        hyper-parameters when they are set (checkpoint.py), so ``load_from_checkpoint`` rebuilds the same generator."""
         super().__init__()
         self.input_modality = input_modality
+        if gen is not None and (gen_head is not None or gen_act is not None):
+            raise ValueError("gen_head / gen_act describe the generator the model builds: give them or gen=, not both")
+        self.gen_head, self.gen_act = gen_head, gen_act
         if gen is None or discr is None:
             from .nn import Discriminator, Generator
-            gen = Generator(input_modality) if gen is None else gen
+            gen = Generator(input_modality, head=gen_head or "conv", act=gen_act) if gen is None else gen
             discr = Discriminator(input_modality) if discr is None else discr
         self.gen, self.discr = gen, discr
         self.recon_factor, self.lr, self.batch_size = recon_factor, lr, batch_size

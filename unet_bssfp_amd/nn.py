@@ -57,6 +57,8 @@ def set_compute_dtype(module: nn.Module, dtype: torch.dtype) -> nn.Module:
         dtype = torch.bfloat16
         if any(isinstance(m, _ADN) and hasattr(m, "A") for m in module.modules()):
             raise NotImplementedError("e4m3 operands with a PReLU network: not verified, use bf16")
+        if any(isinstance(m, ResidualUnit) for m in module.modules()):
+            raise NotImplementedError("e4m3 operands with ResNet input heads: not verified, use bf16")
     assert dtype in (torch.float32, torch.bfloat16)
     for m in module.modules():
         if isinstance(m, _Mi355Module):
@@ -216,6 +218,105 @@ class DownSampleConv(_Mi355Module):
 
     def forward(self, x):
         return self._from_act(self.forward_act(self._to_act(x)), self.conv.out_channels)
+
+
+# ------------------------------------------------------------------------------------------
+# monai.networks.blocks.ResidualUnit (module/parameter names follow MONAI's state_dict)
+class _ResADN(nn.Module):
+    def __init__(self, channels, batch: bool):
+        super().__init__()
+        self.N = _NormParams(channels, batch=batch)
+
+
+class _ResSubunit(nn.Module):
+    """MONAI Convolution(k3, s1, p1, adn_ordering="NDA") of a ResidualUnit: the parameter holder ``conv`` + ``adn.N``"""
+
+    def __init__(self, cin, cout, batch: bool):
+        super().__init__()
+        self.conv = Conv3d(cin, cout, 3, 1, 1, bias=True)
+        self.adn = _ResADN(cout, batch)
+
+
+class ResidualUnit(_Mi355Module):
+    """monai.networks.blocks.ResidualUnit(spatial_dims=3, in_channels, out_channels, strides=1, kernel_size=3, subunits,
+    adn_ordering="NDA", act, norm, dropout=None, bias=True, last_conv_only=False): ``subunits`` x (Conv3d k3 p1 -> norm -> act), plus
+    the residual branch -- the input itself, or a 1x1x1 convolution when the channel counts differ -- and NO activation after
+    the sum.  The thesis's input block is ResidualUnit(3, cin, 24, subunits=3, act="RELU", norm="BATCH")
+    (doc/thesis/03-methods.tex:763-764).  MONAI is not a dependency: parity with it is unpinned; tests/resunit_ref.py restates the
+    block in plain torch under MONAI's names and pins this class against that.
+
+    state_dict: conv.unit{i}.conv.{weight,bias}, conv.unit{i}.adn.N.{weight,bias[,running_mean,running_var,num_batches_tracked]},
+    residual.{weight,bias} (projection only); construction order and initialisation are the torch modules'.
+    norm: "BATCH", or ("INSTANCE", {"affine": True}); act: "RELU" or a LeakyReLU (parse_act), no trained slope.
+    The last subunit's norm + act, the residual branch and the sum are ONE launch (Fn.ResTailFn) when ``fuse_tail`` is set, the
+    activation is ReLU and the kernel takes the channel counts; otherwise a norm + act launch, the 1x1x1 convolution and an add."""
+
+    fuse_tail = True        # False: the tail from the existing parts (the A/B partner of tools/bench_resnet_head.py, and the tests' second path)
+
+    def __init__(self, spatial_dims=3, in_channels=1, out_channels=1, strides=1, kernel_size=3, subunits=2, act="RELU", norm="BATCH",
+                 dropout=None, bias=True):
+        super().__init__()
+        if spatial_dims != 3:
+            raise NotImplementedError("ResidualUnit: only spatial_dims=3 is implemented")
+        if strides != 1 or kernel_size != 3:
+            raise NotImplementedError("ResidualUnit: only strides=1, kernel_size=3 (the thesis's input block) is implemented")
+        if dropout:
+            raise NotImplementedError("ResidualUnit: dropout is not implemented (the thesis's input block has none)")
+        if not bias:
+            raise NotImplementedError("ResidualUnit: bias=False is not implemented")
+        kind, slope, init = parse_act(act)
+        if kind != "leakyrelu" or init is not None:
+            raise NotImplementedError("ResidualUnit: an activation with a trained slope (PReLU) is not implemented")
+        name, kw = (norm[0], dict(norm[1]) if len(norm) > 1 else {}) if isinstance(norm, (tuple, list)) else (norm, {})
+        name = str(name).lower()
+        if name == "batch":
+            self.norm_kind = "batch"
+        elif name == "instance":
+            if not kw.get("affine", False):
+                raise NotImplementedError("ResidualUnit: InstanceNorm without affine parameters is not implemented; "
+                                          "pass norm=('INSTANCE', {'affine': True})")
+            self.norm_kind = "instance"
+        else:
+            raise NotImplementedError(f"ResidualUnit: norm={norm!r}: only BATCH and ('INSTANCE', {{'affine': True}}) are implemented")
+        self.in_channels, self.out_channels, self.subunits = in_channels, out_channels, max(1, int(subunits))
+        batch = self.norm_kind == "batch"
+        self.conv = nn.Sequential()
+        cin = in_channels
+        for i in range(self.subunits):
+            self.conv.add_module(f"unit{i:d}", _ResSubunit(cin, out_channels, batch))
+            cin = out_channels
+        self.residual = Conv3d(in_channels, out_channels, 1, 1, 0, bias=True) if in_channels != out_channels else nn.Identity()
+        self.cfg = Fn.NormCfg(self.norm_kind, out_channels, eps=1e-5, momentum=0.1, slope=slope)
+
+    def _fused(self, cp: int) -> bool:
+        proj = isinstance(self.residual, Conv3d)
+        return self.fuse_tail and self.cfg.slope == 0.0 and ops.restail_supported(cp, self.in_channels, proj)
+
+    def forward_act(self, x):
+        batch = self.norm_kind == "batch"
+        stats = self.training or not batch                 # statistics of the batch itself (else BatchNorm's running ones)
+        n, d, h, w = x.shape[:4]
+        cp = round_up(self.out_channels, 16)
+        small = stats and ops.norm_is_small(n, d, h, w, cp)
+        a = x
+        for i, unit in enumerate(self.conv):
+            last = i == self.subunits - 1
+            bn = unit.adn.N
+            running = (bn.running_mean, bn.running_var, bn.num_batches_tracked if self.training else None) if batch else (None,) * 3
+            fused = last and self._fused(cp)
+            z, part = unit.conv.forward_act(a, want_stats=stats and (fused or not small), zero_bias_grad=stats)
+            if fused:
+                proj = isinstance(self.residual, Conv3d)
+                return Fn.ResTailFn.apply(z, part, x, bn.weight, bn.bias, unit.conv.bias, self.residual.weight if proj else None,
+                                          self.residual.bias if proj else None, self.residual.spec if proj else None, self.cfg,
+                                          self.training, *running)
+            a = Fn.NormActFn.apply(z, part if (stats and not small) else None, bn.weight, bn.bias, unit.conv.bias, self.cfg,
+                                   self.training, running[0], running[1], False, running[2], small)
+        res = self.residual.forward_act(x)[0] if isinstance(self.residual, Conv3d) else x
+        return a + res
+
+    def forward(self, x):
+        return self._from_act(self.forward_act(self._to_act(x)), self.out_channels)
 
 
 class Discriminator(_Mi355Module):
@@ -636,17 +737,29 @@ def backward_stages(net: nn.Module, modality, frozen=()):
 class Generator(_Mi355Module):
     """src/model.py:15-39: modality head (1x1x1 DownSampleConv) -> BasicUNet(24 -> 6)."""
 
-    def __init__(self, input_modality, dropout=0.05, features=(32, 64, 128, 256, 512, 32), act=None):
+    HEAD_CHANNELS = {"dwi-tensor": 6, "pc-bssfp": 24, "bssfp": 24, "t1w": 6}
+
+    def __init__(self, input_modality, dropout=0.05, features=(32, 64, 128, 256, 512, 32), act=None, head="conv"):
         """act: the U-Net's activation as BasicUNet takes it (None: MONAI's default LeakyReLU(0.1)); "PReLU" is the thesis's
-        choice (doc/thesis/03-methods.tex:760).  The modality heads keep their LeakyReLU(0.2)."""
+        choice (doc/thesis/03-methods.tex:760).
+        head: "conv" -- the reference's heads, one 1x1x1 DownSampleConv with LeakyReLU(0.2) shared by each pair of modalities;
+        "resnet" -- the thesis's input blocks (doc/thesis/03-methods.tex:763-764): one ResidualUnit(3, cin, 24, subunits=3,
+        act="RELU", norm="BATCH") per modality, four separate modules (a TRANSFER to 'bssfp' does not move the head a
+        'pc-bssfp' run trained)."""
         super().__init__()
         self.input_modality = input_modality
-        dwi_tensor_input = DownSampleConv(6, 24, kernel=1, strides=1, padding=0)
-        bssfp_input = DownSampleConv(24, 24, kernel=1, strides=1, padding=0)
+        if head == "conv":
+            dwi_tensor_input = DownSampleConv(6, 24, kernel=1, strides=1, padding=0)
+            bssfp_input = DownSampleConv(24, 24, kernel=1, strides=1, padding=0)
+            heads = {"dwi-tensor": dwi_tensor_input, "pc-bssfp": bssfp_input, "bssfp": bssfp_input, "t1w": dwi_tensor_input}
+        elif head == "resnet":
+            heads = {m: ResidualUnit(3, cin, 24, subunits=3, act="RELU", norm="BATCH") for m, cin in self.HEAD_CHANNELS.items()}
+        else:
+            raise ValueError(f"unknown head {head!r} (choose 'conv' or 'resnet')")
+        self.head = head
         kw = {} if act is None else {"act": act}
         unet = BasicUNet(spatial_dims=3, in_channels=24, out_channels=6, features=features, dropout=dropout, **kw)
-        self.blocks = nn.ModuleDict({"dwi-tensor": dwi_tensor_input, "pc-bssfp": bssfp_input,
-                                     "bssfp": bssfp_input, "t1w": dwi_tensor_input, "unet": unet})
+        self.blocks = nn.ModuleDict({**heads, "unet": unet})
 
     emit_s2d = False      # set by the training harness: also hand S(output) to the PatchGAN (Fn.GenOutFn), bf16 mode, even extents
 

@@ -779,6 +779,51 @@ def normact_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, seed, bat
     return dz, dgamma, dbeta
 
 
+RESTAIL_MAX_C, RESTAIL_MAX_CX = 64, 32      # csrc/resunit.hip: padded output channels / input channels of the projection
+
+
+def restail_supported(c: int, cx: int, projection: bool) -> bool:
+    """Does mi355_restail_fwd take c (padded) output channels and, for a projection residual, cx input channels?"""
+    return c <= RESTAIL_MAX_C and (not projection or cx <= RESTAIL_MAX_CX)
+
+
+def restail_fwd(z, x, groups, mean, rstd, gamma, beta, n_real, cx, rw=None, rb=None):
+    """y = ReLU(Norm(z)) + residual(x) in one launch (mi355_restail_fwd): the tail of nn.ResidualUnit.  z: the last
+    convolution's output (n, d, h, w, c); x: the block's input on the same grid; mean / rstd: f32 [groups][c]; gamma / beta: f32
+    [n_real] or None.  rw=None: the residual is x itself (cx == n_real).  rw (f32, (n_real, cx[, 1, 1, 1]), contiguous) and rb
+    (f32 [n_real] or None): the residual is the 1x1x1 convolution of x's first cx channels, on bf16(rw) in bf16 mode.  Returns
+    y (shape and dtype of z), every element written (channels >= n_real: zeros)."""
+    require_cuda(z, x, mean, rstd, gamma, beta, rw, rb)
+    n, dd, h, w, c = z.shape
+    rows = n * dd * h * w
+    if not (is_act(z) and is_act(x)) or x.dtype != z.dtype or tuple(x.shape[:4]) != (n, dd, h, w):
+        raise ValueError(f"restail_fwd: z {tuple(z.shape)} {z.dtype} and x {tuple(x.shape)} {x.dtype} must be NDHWC activations "
+                         "of one dtype on one grid")
+    if rows % groups or not 0 < n_real <= c or cx > x.shape[4]:
+        raise ValueError(f"restail_fwd: rows={rows} groups={groups} n_real={n_real} c={c} cx={cx} x channels={x.shape[4]}")
+    for t in (mean, rstd):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != groups * c:
+            raise ValueError(f"norm statistics hold {t.numel()} values for {groups} group(s) x {c} channels")
+    for t in (gamma, beta, rb):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n_real):
+            raise ValueError(f"restail_fwd: gamma / beta / rb must be f32 vectors of {n_real} values")
+    if rw is not None and (rw.dtype != torch.float32 or not rw.is_contiguous() or rw.numel() != n_real * cx):
+        raise ValueError(f"restail_fwd: rw must be f32 ({n_real}, {cx}), got {tuple(rw.shape)} {rw.dtype}")
+    if rw is None and (rb is not None or cx != n_real or x.shape[4] < c):
+        raise ValueError("restail_fwd: the identity residual takes no bias and an x of the output's (padded) channel count")
+    out = new_act(n, dd, h, w, c, z.dtype, z.device)
+    d = _lib.ResTailDesc()
+    d.z, d.ldz = z.data_ptr(), act_ld(z)
+    d.x, d.ldx, d.cx = x.data_ptr(), act_ld(x), cx
+    d.y, d.ldy = out.data_ptr(), act_ld(out)
+    d.c, d.n_real, d.rows_per_group, d.groups = c, n_real, rows // groups, groups
+    d.mean, d.rstd, d.gamma, d.beta = mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), _ptr(beta)
+    d.rw, d.rb = _ptr(rw), _ptr(rb)
+    d.dtype, d.layout = _DT[z.dtype], 0
+    _lib.check(_lib.load().mi355_restail_fwd(C.byref(d), _stream()), "restail_fwd")
+    return out
+
+
 # tensors of up to 512 K elements (1 MB bf16: 8^3 x 512, 16^3 x 128 ...) with >= 64 channels take the one-launch kernels.  Measured in
 # the full step (interleaved A/B, bench.py --small-norm-elements): 1 M (16^3 x 256 included) 12.42 ms, 600 K 12.21, 300 K 12.23,
 # never 12.33 -- one workgroup per 16 bytes of channels is too few workgroups for a 2 MB tensor

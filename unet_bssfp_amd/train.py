@@ -3,7 +3,8 @@
     python -m unet_bssfp_amd.train manifest.json
 
 reads ``{"modality": ..., "dirpath": ..., "train": [{image name: NIfTI path, ...}, ...], "val": [...]}`` (optional:
-``"max_epochs"``, ``"ckpt_path"``, ``"seed"``, ``"device"``), uploads every subject once (``data.subjects_from_nifti``)
+``"max_epochs"``, ``"ckpt_path"``, ``"seed"``, ``"device"``, and the generator's ``"head"`` (``"conv"`` | ``"resnet"``) and
+``"act"`` -- ``{"stages": [...], "head": "resnet", "act": "prelu"}`` is the thesis's network and workflow), uploads every subject once (``data.subjects_from_nifti``)
 and trains through two ``data.PatchQueue``s with the reference's arguments; like the reference's ``val_set``
 (src/data_module.py:146-147) the validation queue augments as the training queue does.
 
@@ -101,18 +102,19 @@ def main(argv=None) -> int:
         manifest = json.load(f)
     device, modality = manifest.get("device", "cuda:0"), manifest["modality"]
     seed = int(manifest.get("seed", 0))
+    model_kw = {k: manifest[m] for m, k in (("head", "gen_head"), ("act", "gen_act")) if manifest.get(m) is not None}
     train = [subjects_from_nifti(files, device) for files in manifest["train"]]
     val = [subjects_from_nifti(files, device) for files in manifest["val"]]
     if "stages" in manifest:
         epochs = manifest.get("max_epochs", 50)
         best = train_staged(lambda state, m: (PatchQueue(train, m, seed=seed), PatchQueue(val, m, seed=seed + 1) if val else None),
                             modality, manifest["dirpath"], stages=manifest["stages"], ckpt_path=manifest.get("ckpt_path"),
-                            max_epochs=epochs if isinstance(epochs, dict) else int(epochs), device=device)
+                            max_epochs=epochs if isinstance(epochs, dict) else int(epochs), device=device, **model_kw)
         print("\n".join(best))
         return 0
     best = train_model(PatchQueue(train, modality, seed=seed), PatchQueue(val, modality, seed=seed + 1) if val else None,
                        modality, manifest["dirpath"], ckpt_path=manifest.get("ckpt_path"),
-                       max_epochs=int(manifest.get("max_epochs", 50)), device=device)
+                       max_epochs=int(manifest.get("max_epochs", 50)), device=device, **model_kw)
     print(best)
     return 0
 
