@@ -643,6 +643,41 @@ int mi355_patch_queue_gather(const mi355_queue_load* loads, int32_t nloads, cons
                              int32_t pd, int32_t ph, int32_t pw, float padding_value, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The patch queue with a spatial transform (tio.RandomFlip, tio.RandomAffine in front of the keep= copy) fused into
+ * the gather: the resampled volume is never materialised,
+ *     out_j[b][ch][z][y][x] = A_b( Tens_{l,j}( trilinear( P(src_j), M_l (o_b + (z, y, x), 1) ) ) ).
+ * P, o_b and A_b are those of mi355_patch_queue_gather; bias coordinates and noise keys come from the OUTPUT position.
+ *   spatial[l]     : m = the first three rows of the index-space matrix of load l, in target (padded) coordinates, with
+ *                    the coordinate arithmetic, inside test (against the target extent) and clamped corners of
+ *                    mi355_rigid_resample; a corner on a pad voxel of P reads padding_value.  t6 = a row-major 6 x 6
+ *                    matrix followed by a 6-vector: in an image with tensor[j] != 0 (exactly 6 channels: dxx, dxy, dxz,
+ *                    dyy, dyz, dzz) an inside voxel becomes n'_i = t6[36 + i] + sum_j t6[6 i + j] n_j, six fmas with j in
+ *                    order.  The fill of an outside voxel is not mapped.
+ *   resampling[l * nimages + j] : resample == 0 reads source (l, j) as is, exactly as mi355_patch_queue_gather does (no
+ *                    tensor map either).  Otherwise an outside voxel of channel c gets channel_min[2 c + 1] (DEVICE memory,
+ *                    the (sum, min) pairs of mi355_channel_sum_min) when channel_min != NULL, else `fill`.
+ * One lane owns 4 consecutive output voxels when pw % 4 == 0 and every output is 16-byte aligned, else one.  Chunked as
+ * mi355_patch_queue_gather.  No atomics, no scratch, no workspace, no host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mi355_queue_spatial {
+  float m[12];
+  float t6[42];
+} mi355_queue_spatial;
+
+typedef struct mi355_queue_resampling {
+  const double* channel_min;
+  float fill;
+  int32_t resample;
+} mi355_queue_resampling;
+
+int mi355_patch_queue_gather_spatial(const mi355_queue_load* loads, const mi355_queue_spatial* spatial, int32_t nloads,
+                                     const mi355_queue_source* sources, const mi355_queue_resampling* resampling,
+                                     const int32_t* channels, const int32_t* augmented, const int32_t* tensor,
+                                     float* const* outs, int32_t nimages, const int32_t* patches, int32_t npatches,
+                                     int32_t td, int32_t th, int32_t tw, int32_t pd, int32_t ph, int32_t pw,
+                                     float padding_value, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * k-space and blur augmentations (tio.RandomGhosting, tio.RandomSpike, tio.RandomBlur) without an FFT: one small dense
  * matrix applied along one axis of a contiguous f32 (C, D, H, W) tensor (axis 0 = D, 1 = H, 2 = W), out of place,
  *     out[c][..i..] = sum_j M[i][j] * x[c][..j..],   M row-major [N][N] f32 in DEVICE memory.

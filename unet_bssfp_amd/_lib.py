@@ -78,6 +78,14 @@ class QueueSource(C.Structure):
     _fields_ = [("src", _vp), ("d", _i32), ("h", _i32), ("w", _i32)]
 
 
+class QueueSpatial(C.Structure):
+    _fields_ = [("m", _f32 * 12), ("t6", _f32 * 42)]
+
+
+class QueueResampling(C.Structure):
+    _fields_ = [("channel_min", _vp), ("fill", _f32), ("resample", _i32)]
+
+
 EPOCH_MAX_SCALARS = 32          # MI355_EPOCH_MAX_SCALARS
 
 
@@ -174,6 +182,9 @@ _SIGNATURES = {
     "mi355_aug_noise": (C.c_int, [_vp, _vp, _i64, _f32, _f32, C.c_uint64, _vp]),
     "mi355_patch_queue_gather": (C.c_int, [C.POINTER(QueueLoad), _i32, C.POINTER(QueueSource), _vp, _vp, _vp, _i32,
                                            _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "mi355_patch_queue_gather_spatial": (C.c_int, [C.POINTER(QueueLoad), C.POINTER(QueueSpatial), _i32, C.POINTER(QueueSource),
+                                                   C.POINTER(QueueResampling), _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32,
+                                                   _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "mi355_axis_apply": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mi355_axis_apply_complex": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mi355_kspace_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),

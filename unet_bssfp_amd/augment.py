@@ -21,6 +21,7 @@ lists all seven stages.
 """
 from __future__ import annotations
 
+import ctypes as C
 import functools
 import math
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple, Union
@@ -543,6 +544,11 @@ def _rigid_rows(matrix) -> np.ndarray:
     return np.ascontiguousarray(m[:3], dtype=np.float32).reshape(12)
 
 
+def _resampled_like(x: torch.Tensor) -> torch.Tensor:
+    """the output of a resample (``rigid_resample``, ``affine_resample``): the launch writes every voxel of it"""
+    return torch.empty_like(x)
+
+
 def rigid_resample(x: torch.Tensor, matrix, fill: Optional[float] = None) -> torch.Tensor:
     """``sitk.Resample(image, image, transform, sitkLinear, fill)`` on a (C, D, H, W) device tensor with voxel spacing 1:
     output voxel ``i`` reads the input at the continuous index ``matrix @ (i, 1)``, trilinearly, inside
@@ -551,7 +557,7 @@ def rigid_resample(x: torch.Tensor, matrix, fill: Optional[float] = None) -> tor
     x = _check(x)
     m = _rigid_rows(matrix)
     cmin = channel_sum_min(x) if fill is None else None
-    out = torch.empty_like(x)
+    out = _resampled_like(x)
     _lib.check(_lib.load().mi355_rigid_resample(x.data_ptr(), out.data_ptr(), *x.shape, m.ctypes.data,
                                                 None if cmin is None else cmin.data_ptr(),
                                                 0.0 if fill is None else float(fill), _stream()), "rigid_resample")
@@ -688,3 +694,227 @@ def reference_full_transform() -> list:
     """all seven stages of the reference's training transform, src/data_module.py:131-139, in its order and with its
     arguments: ``RandomMotion(p=0.1)`` first, then ``reference_training_transform()``"""
     return [RandomMotion(p=0.1)] + reference_training_transform()
+
+
+# ---- spatial stages: host mathematics (f64) ---------------------------------------------------------------------------
+#
+# RandomFlip and RandomAffine (DESIGN.md 8.17).  A spatial stage is an index-space matrix, as RandomMotion's copies are:
+# output voxel ``i`` reads the input at ``M (i, 1)``.  Several stages compose into one matrix and the volume is resampled
+# once, inside the patch gather (csrc/spatial.hip).  Axes (0, 1, 2) of (C, D, H, W) are x, y, z.  TorchIO is absent: its
+# scale direction, its centre, its LPS sign flips and its random streams are not reproduced (**parity unpinned**).
+
+TENSOR_COMPONENTS = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))   # dxx, dxy, dxz, dyy, dyz, dzz (eval.ERROR_COLUMNS)
+
+
+def flip_index_matrix(axes: Sequence[int], shape: Sequence[int]) -> np.ndarray:
+    """mirroring along ``axes`` as a 4 x 4 f64 index-space matrix: ``s_a = (T_a - 1) - i_a`` on a flipped axis.  Exact in
+    f32, and trilinear interpolation at an integer coordinate returns the voxel itself."""
+    m = np.eye(4)
+    for a in axes:
+        if a not in (0, 1, 2):
+            raise ValueError(f"axes must be among 0, 1, 2, got {a}")
+        m[a, a] = -1.0
+        m[a, 3] = float(int(shape[a]) - 1)
+    return m
+
+
+def affine_index_matrix(scales: Sequence[float], degrees: Sequence[float], translation: Sequence[float],
+                        shape: Sequence[int]) -> np.ndarray:
+    """``p_in = c + R diag(1 / s) (i - c) + t`` as a 4 x 4 f64 index-space matrix, ``R = Rz Rx Ry`` as in
+    ``euler_index_matrix`` and ``c = (shape - 1) / 2``, the centre of the voxel grid; ``s > 1`` zooms in"""
+    s = np.asarray(scales, dtype=np.float64).reshape(3)
+    if not np.all(s > 0):
+        raise ValueError(f"scales must be positive, got {tuple(s)}")
+    a = euler_index_matrix(degrees, (0, 0, 0), (0, 0, 0))[:3, :3] @ np.diag(1.0 / s)
+    c = 0.5 * (np.asarray(shape, dtype=np.float64).reshape(3) - 1.0)
+    m = np.eye(4)
+    m[:3, :3] = a
+    m[:3, 3] = c + np.asarray(translation, dtype=np.float64).reshape(3) - a @ c
+    return m
+
+
+def compose_index_matrices(matrices) -> np.ndarray:
+    """``M = M_1 M_2 ...`` in list order: resampling through ``M`` once is resampling through ``M_1``, then ``M_2``, ..."""
+    m = np.eye(4)
+    for k in matrices:
+        m = m @ np.asarray(k, dtype=np.float64)
+    return m
+
+
+def check_tensor_rescale(rescale) -> Optional[np.ndarray]:
+    """``None`` or a (6, 2) f64 array of per-component (min, max), the layout of the reference's rescale_args_dwi.txt"""
+    if rescale is None:
+        return None
+    r = np.asarray(rescale, dtype=np.float64)
+    if r.shape != (6, 2) or not np.all(np.isfinite(r)) or np.any(r[:, 0] == r[:, 1]):
+        raise ValueError(f"a tensor rescale is a finite (6, 2) array of (min, max) with min != max, got shape {r.shape}")
+    return r
+
+
+def tensor_reorientation(matrix, rescale=None) -> Tuple[np.ndarray, np.ndarray]:
+    """how a diffusion tensor turns with the volume, -> (T6 (6, 6), t6 (6,)) f64 with ``vec(D') = T6 vec(D) + t6`` on the
+    components dxx, dxy, dxz, dyy, dyz, dzz.  ``F = inv(M[:3, :3])`` carries input points to output points; its
+    finite-strain rotation ``R_t = U V^T`` (SVD of ``F``) turns the tensor, ``D' = R_t D R_t^T``; a reflection stays a
+    reflection, a scale does not touch the tensor.  With ``rescale`` ((6, 2): min, max per component) the map acts on
+    values normalised as ``n = (D - lo) / w``, ``w = |max - min|``: ``T6 <- W^-1 T6 W``, ``t6 = W^-1 (T6 lo - lo)``."""
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape not in ((4, 4), (3, 4), (3, 3)):
+        raise ValueError(f"need a 4 x 4, 3 x 4 or 3 x 3 matrix, got {m.shape}")
+    u, _, vt = np.linalg.svd(np.linalg.inv(m[:3, :3]))
+    r = u @ vt
+    t6 = np.zeros((6, 6))
+    for col, (a, b) in enumerate(TENSOR_COMPONENTS):
+        e = np.zeros((3, 3))
+        e[a, b] = e[b, a] = 1.0
+        d = r @ e @ r.T
+        t6[:, col] = [d[i, j] for i, j in TENSOR_COMPONENTS]
+    rescale = check_tensor_rescale(rescale)
+    if rescale is None:
+        return t6, np.zeros(6)
+    lo, w = rescale[:, 0], np.abs(rescale[:, 1] - rescale[:, 0])
+    return t6 * w[None, :] / w[:, None], (t6 @ lo - lo) / w
+
+
+NOT_A_TENSOR = "not a tensor"   # affine_resample(tensor_rescale=...): the image is no tensor image (None = one without rescale)
+
+
+def affine_resample(x: torch.Tensor, matrix, fill: Optional[float] = None, tensor_rescale=NOT_A_TENSOR) -> torch.Tensor:
+    """``rigid_resample`` through any invertible index-space matrix, as the patch queue does it: the spatial gather
+    (``mi355_patch_queue_gather_spatial``) with one patch that is the whole volume, so the queue and this function share
+    every bit.  ``fill=None``: an outside voxel gets the minimum of its channel, read on the device (no synchronisation).
+    ``tensor_rescale`` = ``None`` or a (6, 2) array: ``x`` is a tensor image (6 channels) and every inside voxel is
+    reoriented by ``tensor_reorientation(matrix, tensor_rescale)``; the fill is not."""
+    x = _check(x)
+    sp = _lib.QueueSpatial()
+    sp.m[:] = _rigid_rows(matrix).tolist()
+    tensor = tensor_rescale is not NOT_A_TENSOR
+    if tensor:
+        if x.shape[0] != 6:
+            raise ValueError(f"a tensor image has 6 channels (dxx, dxy, dxz, dyy, dyz, dzz), got {x.shape[0]}")
+        sp.t6[:] = _tensor_rows(matrix, tensor_rescale).tolist()
+    cmin = channel_sum_min(x) if fill is None else None
+    out = _resampled_like(x)
+    rs = _lib.QueueResampling(None if cmin is None else cmin.data_ptr(), 0.0 if fill is None else float(fill), 1)
+    src = _lib.QueueSource(x.data_ptr(), *x.shape[1:])
+    one = lambda v: (C.c_int32 * 1)(v)
+    _lib.check(_lib.load().mi355_patch_queue_gather_spatial(
+        (_lib.QueueLoad * 1)(), (_lib.QueueSpatial * 1)(sp), 1, (_lib.QueueSource * 1)(src), (_lib.QueueResampling * 1)(rs),
+        one(x.shape[0]), one(0), one(int(tensor)), (C.c_void_p * 1)(out.data_ptr()), 1, (C.c_int32 * 4)(0, 0, 0, 0), 1,
+        *x.shape[1:], *x.shape[1:], 0.0, _stream()), "patch_queue_gather_spatial")
+    return out
+
+
+def _tensor_rows(matrix, rescale) -> np.ndarray:
+    """``tensor_reorientation`` as 42 f32: the 6 x 6 matrix row-major, then the 6-vector (the one rounding)"""
+    t6, t = tensor_reorientation(matrix, rescale)
+    return np.concatenate([t6.reshape(36), t]).astype(np.float32)
+
+
+class _Spatial(_Random):
+    """a stage that moves voxels: ``matrix(params, shape)`` is its index-space matrix.  It applies to EVERY image of a
+    subject with one parameter set, the target included, and a tensor image is reoriented with it."""
+
+    fill: Optional[float] = 0.0        # what an outside voxel gets; None = the channel minimum
+
+    def apply(self, x, params, tensor_rescale=NOT_A_TENSOR):
+        x = _check(x)
+        if not self.has_effect(params):
+            return x
+        return affine_resample(x, self.matrix(params, x.shape[1:]), self.fill, tensor_rescale)
+
+    def __call__(self, subject, tensor_images: Optional[Dict] = None):
+        """as ``_Random.__call__``: one decision and one parameter set per call for every image of the subject;
+        ``tensor_images = {name: rescale or None}`` names the images that hold diffusion tensors"""
+        if torch.rand(1).item() >= self.p:
+            return subject
+        params = self.sample()
+        if isinstance(subject, torch.Tensor):
+            return self.apply(subject, params)
+        tensor_images = tensor_images or {}
+        return {k: ({**v, "data": self.apply(v["data"], params, tensor_images.get(k, NOT_A_TENSOR))}
+                    if isinstance(v, dict) and "data" in v else v) for k, v in subject.items()}
+
+
+class RandomFlip(_Spatial):
+    """``tio.RandomFlip``: each listed axis is mirrored with probability ``flip_probability``.  params = the tuple of axes
+    that flip.  Axes are 0, 1, 2 of (C, D, H, W); TorchIO's anatomical axis labels are not built.  Parity unpinned."""
+
+    def __init__(self, axes: Union[int, Tuple[int, ...]] = 0, flip_probability: float = 0.5, p: float = 1.0):
+        super().__init__(p)
+        self.axes = (axes,) if isinstance(axes, int) else tuple(axes)
+        if not self.axes or any(not isinstance(a, int) or a not in (0, 1, 2) for a in self.axes) \
+                or len(set(self.axes)) != len(self.axes):
+            raise ValueError(f"axes must be distinct and among 0, 1, 2, got {axes}")
+        if not 0.0 <= flip_probability <= 1.0:
+            raise ValueError(f"flip_probability must be in [0, 1], got {flip_probability}")
+        self.flip_probability = float(flip_probability)
+
+    def sample(self) -> Tuple[int, ...]:
+        """one ``torch.rand`` per listed axis"""
+        return tuple(a for a in self.axes if torch.rand(1).item() < self.flip_probability)
+
+    @staticmethod
+    def has_effect(params) -> bool:
+        return len(params) > 0
+
+    @staticmethod
+    def matrix(params, shape) -> np.ndarray:
+        return flip_index_matrix(params, shape)
+
+
+class AffineParams(NamedTuple):
+    """one RandomAffine draw: (3,) f64 each"""
+    scales: np.ndarray
+    degrees: np.ndarray
+    translation: np.ndarray
+
+
+class RandomAffine(_Spatial):
+    """``tio.RandomAffine``: a scale per axis from ``(1 - scales, 1 + scales)``, Euler angles in degrees and a translation
+    in voxels, about the centre of the grid (``affine_index_matrix``).  Only ``center='image'``, linear interpolation and
+    ``default_pad_value`` = ``'minimum'`` (the channel minimum) or a number are built.  Parity unpinned: TorchIO's scale
+    direction, centre and random streams are not reproduced."""
+
+    def __init__(self, scales: Range = 0.1, degrees: Range = 10, translation: Range = 0, isotropic: bool = False,
+                 center: str = "image", default_pad_value: Union[str, float] = "minimum",
+                 image_interpolation: str = "linear", p: float = 1.0):
+        super().__init__(p)
+        if image_interpolation != "linear":
+            raise NotImplementedError(f"image_interpolation={image_interpolation!r}: only 'linear' is built")
+        if center != "image":
+            raise NotImplementedError(f"center={center!r}: only 'image' is built")
+        if isinstance(default_pad_value, str):
+            if default_pad_value != "minimum":
+                raise NotImplementedError(f"default_pad_value={default_pad_value!r}: only 'minimum' or a number is built")
+            self.fill = None
+        elif isinstance(default_pad_value, (int, float)) and not isinstance(default_pad_value, bool) \
+                and math.isfinite(default_pad_value):
+            self.fill = float(default_pad_value)
+        else:
+            raise ValueError(f"default_pad_value must be 'minimum' or a finite number, got {default_pad_value!r}")
+        if isinstance(scales, (int, float)):
+            self.scales_range = (1.0 - float(scales), 1.0 + float(scales))
+        else:
+            self.scales_range = _range(scales, False)
+        if not 0 < self.scales_range[0] <= self.scales_range[1]:
+            raise ValueError(f"scales={scales}: need 0 < lowest <= highest scale")
+        self.degrees_range, self.translation_range = _range(degrees, True), _range(translation, True)
+        self.isotropic, self.center, self.default_pad_value = bool(isotropic), center, default_pad_value
+        self.image_interpolation = image_interpolation
+
+    def sample(self) -> AffineParams:
+        """scales, then degrees, then translation, 3 values each; with ``isotropic`` the first scale serves all axes"""
+        draw = lambda lo, hi: (torch.rand(3, dtype=torch.float64) * (hi - lo) + lo).numpy()
+        scales = draw(*self.scales_range)
+        if self.isotropic:
+            scales = np.full(3, scales[0])
+        return AffineParams(scales, draw(*self.degrees_range), draw(*self.translation_range))
+
+    @staticmethod
+    def has_effect(params) -> bool:
+        s, d, t = (np.asarray(v, dtype=np.float64) for v in params)
+        return bool(np.any(s != 1) or np.any(d != 0) or np.any(t != 0))
+
+    @staticmethod
+    def matrix(params, shape) -> np.ndarray:
+        return affine_index_matrix(*params, shape)

@@ -22,6 +22,7 @@
 // the device.  Every gather index is clamped, so no transform can make a load leave the volume; a NaN coordinate fails the
 // inside test.  No atomics, no scratch, no host synchronisation.
 #include "common.h"
+#include "resample_core.h"
 
 namespace {
 
@@ -33,39 +34,9 @@ constexpr int kChunks = kMaxN / kRows / kWaves;   // chunks per wave at N = 128
 constexpr int kThreads = kWaves * 64;
 constexpr int kMaxImages = MI355_MOTION_MAX_IMAGES;
 
-// s_a = m[4 a] i_D + m[4 a + 1] i_H + m[4 a + 2] i_W + m[4 a + 3]: the first three rows of the index-space matrix
-struct Rigid { float m[12]; };
-
 typedef __attribute__((address_space(4))) float ConstF;   // a float in the constant address space (scalar loads)
 
 __device__ __forceinline__ int swz(int j, int t) { return j * kCols + (t ^ (j & (kCols - 1))); }
-
-__device__ __forceinline__ float lerp(float a, float b, float t) { return fmaf(t, b - a, a); }
-
-// one output voxel (id, ih, iw) of one channel `xc`
-__device__ __forceinline__ float sample(const float* __restrict__ xc, const Rigid& q, int d, int h, int w, int id, int ih,
-                                        int iw, float fill) {
-  const float fd = (float)id, fh = (float)ih, fw = (float)iw;
-  const float s0 = fmaf(q.m[2], fw, fmaf(q.m[1], fh, fmaf(q.m[0], fd, q.m[3])));
-  const float s1 = fmaf(q.m[6], fw, fmaf(q.m[5], fh, fmaf(q.m[4], fd, q.m[7])));
-  const float s2 = fmaf(q.m[10], fw, fmaf(q.m[9], fh, fmaf(q.m[8], fd, q.m[11])));
-  const bool inside = s0 >= -0.5f && s0 < (float)d - 0.5f && s1 >= -0.5f && s1 < (float)h - 0.5f && s2 >= -0.5f &&
-                      s2 < (float)w - 0.5f;
-  if (!inside) return fill;
-  const float f0 = floorf(s0), f1 = floorf(s1), f2 = floorf(s2);
-  const float t0 = s0 - f0, t1 = s1 - f1, t2 = s2 - f2;
-  const int a0 = (int)f0, a1 = (int)f1, a2 = (int)f2;                 // -1 .. N - 1
-  const int lo0 = max(a0, 0), hi0 = min(a0 + 1, d - 1);
-  const int lo1 = max(a1, 0), hi1 = min(a1 + 1, h - 1);
-  const int lo2 = max(a2, 0), hi2 = min(a2 + 1, w - 1);
-  const float* __restrict__ p00 = xc + ((long long)lo0 * h + lo1) * w;
-  const float* __restrict__ p01 = xc + ((long long)lo0 * h + hi1) * w;
-  const float* __restrict__ p10 = xc + ((long long)hi0 * h + lo1) * w;
-  const float* __restrict__ p11 = xc + ((long long)hi0 * h + hi1) * w;
-  const float v00 = lerp(p00[lo2], p00[hi2], t2), v01 = lerp(p01[lo2], p01[hi2], t2);
-  const float v10 = lerp(p10[lo2], p10[hi2], t2), v11 = lerp(p11[lo2], p11[hi2], t2);
-  return lerp(lerp(v00, v01, t1), lerp(v10, v11, t1), t0);
-}
 
 struct ResampleArgs {
   const float* x; float* out; const double* cmin;   // cmin: null, or (sum, min) pairs per channel

@@ -16,6 +16,10 @@ reads that tensor as the load's source and fuses only the local stages that foll
 the patches of its load.  ``RandomMotion`` draws one parameter set per augmented image of a load (as TorchIO does per
 image of a subject), the other stages one per load.  Any other transform type raises ``TypeError``.
 
+Spatial stages (``spatial=``: ``augment.RandomFlip``, ``RandomAffine``) sit in front of the ``keep`` copy and move every
+image of a load alike; they are resampled inside the gather (``mi355_patch_queue_gather_spatial``), the
+resampled volume is never materialised, and a diffusion-tensor image is reoriented voxel by voxel.
+
 The plan -- which subjects fill the queue, the stages that fire and their parameters, the patch origins and their order
 -- is host logic driven by the queue's own ``torch.Generator`` and needs no GPU (``next_plan``).  TorchIO is absent: the
 structure follows its Queue (fill, shuffle, pop from the end), but its exact random streams are not reproduced
@@ -36,6 +40,7 @@ _STAGE_KIND = {augment.RandomBiasField: 1, augment.RandomNoise: 2, augment.Rando
 _NONLOCAL = (augment.RandomMotion, augment.RandomGhosting, augment.RandomSpike, augment.RandomBlur)   # staged, never fused
 _SIGN_PRESERVING = (augment.RandomBiasField, augment.RandomGamma, augment.RandomBlur)      # x >= 0 stays >= 0
 _MAX_IMAGES = 4                                                                              # MI355_QUEUE_MAX_IMAGES
+_SPATIAL = (augment.RandomFlip, augment.RandomAffine)                                        # resampled inside the gather
 
 
 def subjects_from_nifti(files: Dict[str, str], device) -> Dict[str, Dict[str, torch.Tensor]]:
@@ -85,12 +90,13 @@ class SubjectLoad(NamedTuple):
     """One load of a subject into the queue: its position in the list given to the queue, the epoch, the running number
     of the fill that loaded it, the seed of the global CPU generator under which its stages were drawn, and the stages
     that fired as (transform, params); the params of a per-image stage (``RandomMotion``) are ``{image name: params}``
-    for the modality and every kept source."""
+    for the modality and every kept source.  ``spatial``: the spatial stages that fired, drawn under ``seed + 1``."""
     subject: int
     epoch: int
     fill: int
     seed: int
     stages: tuple
+    spatial: tuple = ()
 
 
 class PlannedPatch(NamedTuple):
@@ -111,6 +117,18 @@ def _stages_of(transform) -> list:
     return transform
 
 
+def _spatial_stages_of(spatial) -> list:
+    spatial = list(spatial or ())
+    seen = set()
+    for t in spatial:
+        if type(t) not in _SPATIAL:
+            raise TypeError(f"{type(t).__name__} is no spatial stage of the patch queue (supported: RandomFlip, RandomAffine)")
+        if type(t) in seen:
+            raise TypeError(f"two {type(t).__name__} stages cannot be fused into one patch queue")
+        seen.add(type(t))
+    return spatial
+
+
 class PatchQueue:
     """``tio.Queue(subjects_dataset, max_length, samples_per_volume, sampler)`` over device-resident subjects.
 
@@ -122,13 +140,24 @@ class PatchQueue:
 
     ``transform``: the augmentations applied per subject load in list order, fused into the gather or staged before it.  ``None`` (the
     default) means ``augment.reference_augmentation()``, the reference's training transform; ``[]`` augments nothing.
-    The queue keeps no history: ``last_fill`` holds the loads of the current fill only."""
+    The queue keeps no history: ``last_fill`` holds the loads of the current fill only.
+
+    ``spatial``: ``augment.RandomFlip`` / ``RandomAffine`` stages that run in FRONT of the ``keep`` copy, i.e. TorchIO's
+    ``Compose([spatial..., Compose([intensity...], keep=...)])``: a stage that fired moves every image of the load, the
+    kept copy and the augmented target included, so input and target stay a pair.  The stages of a load compose into one
+    matrix and the volume is resampled once, inside the gather (``mi355_patch_queue_gather_spatial``); a batch in which
+    no load has an effective spatial stage takes the plain launch.  They are drawn under a seed derived from the load's
+    own, not from the queue's generator, so a queue with and without ``spatial`` plans the same subjects, seeds,
+    intensity stages and origins.  ``tensor_images = {source name: rescale or None}`` names the image whose six channels
+    are a diffusion tensor, reoriented with the volume (``augment.tensor_reorientation``; a (6, 2) array of (min, max) for
+    normalised data); the default is ``{'dwi-tensor': None}`` when the queue reads that image.  ``None`` or ``[]``
+    (the default) changes nothing: the same draws, the same launch, the same bits."""
 
     def __init__(self, subjects: Sequence[Dict[str, Dict[str, torch.Tensor]]], modality: str, max_length: int = 16,
                  samples_per_volume: int = 8, sampler: Optional[UniformSampler] = None,
                  target_shape: Sequence[int] = (96, 128, 128), transform=None,
                  keep: Optional[Dict[str, str]] = None, seed: int = 0, rank: int = 0, world: int = 1,
-                 padding_value: float = 0.0):
+                 padding_value: float = 0.0, spatial=None, tensor_images: Optional[Dict] = None):
         self.sampler = UniformSampler(64) if sampler is None else sampler
         self.target_shape = _triple(target_shape)
         if min(self.target_shape) <= 0:
@@ -173,6 +202,27 @@ class PatchQueue:
                     ok = ok and float(t.min()) >= 0 and (self.padding_value >= 0 or not pads)
                 self.nonnegative[idx] = ok
         self._check_nonlocal()
+        self.spatial = _spatial_stages_of(spatial)
+        if tensor_images is None:
+            tensor_images = {"dwi-tensor": None} if "dwi-tensor" in names else {}
+        self.tensor_images = {name: augment.check_tensor_rescale(r) for name, r in dict(tensor_images).items()}
+        self._channel_min: Dict[Tuple[int, str], torch.Tensor] = {}   # (subject, image) -> (C, 2) f64 (sum, min) on the device
+        if self.spatial:
+            for name in self.tensor_images:
+                if name not in names:
+                    raise ValueError(f"tensor image '{name}' is not among the images of the queue {names}")
+                if self.channels[name] != 6:
+                    raise ValueError(f"tensor image '{name}' has {self.channels[name]} channels; a diffusion tensor has 6 "
+                                     "(dxx, dxy, dxz, dyy, dyz, dzz)")
+            if len(self.tensor_images) > 1:
+                raise ValueError(f"one tensor image per queue (a load carries one reorientation), got {list(self.tensor_images)}")
+            # 'minimum' fills with the channel minima of crop_or_pad(raw): reduced on the device once per subject image,
+            # here, so that next_batch only passes a pointer
+            if any(t.fill is None for t in self.spatial):
+                for idx, subj in self._by_index.items():
+                    for name in dict.fromkeys(names):
+                        if subj[name][DATA].is_cuda:
+                            self._channel_minimum(idx, name)
         self._staged: Dict[int, Tuple[SubjectLoad, Dict[str, torch.Tensor]]] = {}   # id(load) -> (load, {image: tensor})
         self._gen = torch.Generator().manual_seed(int(seed))
         self.epoch = -1
@@ -262,6 +312,19 @@ class PatchQueue:
                     stages.append((t, params))
         return seed, tuple(stages)
 
+    def _draw_spatial(self, seed: int) -> tuple:
+        """the spatial stages that fire for a load whose intensity stages were drawn under ``seed``: drawn like them, but
+        under ``seed + 1`` and never from the queue's generator, so that they leave every other draw where it was"""
+        if not self.spatial:
+            return ()
+        fired = []
+        with torch.random.fork_rng(devices=[]):
+            torch.default_generator.manual_seed(seed + 1)
+            for t in self.spatial:
+                if torch.rand(1).item() < t.p:
+                    fired.append((t, t.sample()))
+        return tuple(fired)
+
     def _augmented_names(self) -> List[str]:
         """the images of a subject that a batch can ask for augmented: the modality, then each kept source"""
         return [self.modality] + [src for src in self.keep if src != self.modality]
@@ -275,7 +338,7 @@ class PatchQueue:
         for _ in range(n):
             subject = self._order.pop()
             seed, stages = self._draw_stages(subject)
-            load = SubjectLoad(subject, self.epoch, self.fill_count, seed, stages)
+            load = SubjectLoad(subject, self.epoch, self.fill_count, seed, stages, self._draw_spatial(seed))
             loads.append(load)
             patches += [PlannedPatch(load, o) for o in
                         self.sampler.draw(self.target_shape, self.samples_per_volume, self._gen)]
@@ -336,12 +399,34 @@ class PatchQueue:
         last = max((i for i, (t, _) in enumerate(live) if type(t) in _NONLOCAL), default=-1)
         return tuple(live[:last + 1]), tuple(live[last + 1:])
 
+    def spatial_transform(self, load: SubjectLoad) -> Optional[Tuple[np.ndarray, Optional[float]]]:
+        """(M, fill) of a load: the 4 x 4 f64 product of its spatial stages in list order, in target coordinates, and what
+        an outside voxel gets (None = the channel minimum); ``None`` if no stage fired with an effect.  A flip with no
+        axis drawn and an affine with s = 1, zero angles and zero shift are dropped, as ``split_stages`` drops no-ops."""
+        live = [(t, p) for t, p in load.spatial if t.has_effect(p)]
+        if not live:
+            return None
+        fills = [t.fill for t, _ in live if isinstance(t, augment.RandomAffine)]    # a flip leaves no voxel outside
+        return (augment.compose_index_matrices([t.matrix(p, self.target_shape) for t, p in live]),
+                fills[0] if fills else 0.0)
+
+    def _channel_minimum(self, subject: int, name: str) -> torch.Tensor:
+        key = (subject, name)
+        if key not in self._channel_min:
+            x = augment.crop_or_pad(self._by_index[subject][name][DATA], self.target_shape, self.padding_value)
+            self._channel_min[key] = augment.channel_sum_min(x)
+        return self._channel_min[key]
+
     def _staged_source(self, load: SubjectLoad, staged: tuple, name: str) -> torch.Tensor:
-        """chain(crop_or_pad(raw)) through ``staged`` for one image of one load, made once and kept while the load has
-        patches; a per-image stage applies the parameter set of the image it stages"""
+        """chain(affine_resample(crop_or_pad(raw))) through ``staged`` for one image of one load, made once and kept while
+        the load has patches (the resample only if a spatial stage of the load has an effect); a per-image stage applies
+        the parameter set of the image it stages"""
         entry = self._staged.setdefault(id(load), (load, {}))[1]
         if name not in entry:
             x = augment.crop_or_pad(self._by_index[load.subject][name][DATA], self.target_shape, self.padding_value)
+            sp = self.spatial_transform(load)
+            if sp is not None:
+                x = augment.affine_resample(x, sp[0], sp[1], self.tensor_images.get(name, augment.NOT_A_TENSOR))
             for t, params in staged:
                 x = t.apply(x, params[name] if t.per_image else params)
             entry[name] = x
@@ -372,7 +457,8 @@ class PatchQueue:
         return q
 
     def gather(self, plan: Sequence[PlannedPatch], out=None, augmented_target: bool = False):
-        """write the patches of ``plan`` (one launch, or one per chunk of MI355_MAX_PATCHES patches / 4 loads)"""
+        """write the patches of ``plan`` (one launch, or one per chunk of MI355_MAX_PATCHES patches / 4 loads): the plain
+        gather, or the spatial one if a load of the plan has a spatial stage with an effect"""
         imgs = self._images(augmented_target)
         sources = {name: [self._by_index[p.load.subject][name][DATA] for p in plan] for _, name, _ in imgs}
         device = self._by_index[plan[0].load.subject][self.modality][DATA].device
@@ -404,10 +490,34 @@ class PatchQueue:
         augmented = (C.c_int32 * nimg)(*[int(a) for _, _, a in imgs])
         ptrs = (C.c_void_p * nimg)(*[outs[name].data_ptr() for name, _, _ in imgs])
         pat = np.array([[slot[id(p.load)], *p.origin] for p in plan], dtype=np.int32)
-        _lib.check(_lib.load().mi355_patch_queue_gather(
-            qloads, len(loads), qsrc, channels, augmented, ptrs, nimg, pat.ctypes.data_as(C.c_void_p), len(plan),
-            *self.target_shape, *self.patch_size, self.padding_value, torch.cuda.current_stream(device).cuda_stream),
-            "patch_queue_gather")
+        moved = [self.spatial_transform(l) for l in loads]
+        if all(m is None for m in moved):
+            _lib.check(_lib.load().mi355_patch_queue_gather(
+                qloads, len(loads), qsrc, channels, augmented, ptrs, nimg, pat.ctypes.data_as(C.c_void_p), len(plan),
+                *self.target_shape, *self.patch_size, self.padding_value, torch.cuda.current_stream(device).cuda_stream),
+                "patch_queue_gather")
+        else:
+            # one launch serves the whole batch; a load without a spatial stage rides along with every image read as is,
+            # and so does the staged image of a load that has one: its resample was done while staging
+            qsp = (_lib.QueueSpatial * len(loads))()
+            qrs = (_lib.QueueResampling * (len(loads) * nimg))()
+            for li, load in enumerate(loads):
+                if moved[li] is None:
+                    continue
+                m, fill = moved[li]
+                qsp[li].m[:] = augment._rigid_rows(m).tolist()
+                for name, rescale in self.tensor_images.items():
+                    qsp[li].t6[:] = augment._tensor_rows(m, rescale).tolist()
+                for j, (_, src, aug) in enumerate(imgs):
+                    if aug and split[li][0]:
+                        continue
+                    cmin = self._channel_minimum(load.subject, src).data_ptr() if fill is None else None
+                    qrs[li * nimg + j] = _lib.QueueResampling(cmin, 0.0 if fill is None else fill, 1)
+            tensor = (C.c_int32 * nimg)(*[int(src in self.tensor_images) for _, src, _ in imgs])
+            _lib.check(_lib.load().mi355_patch_queue_gather_spatial(
+                qloads, qsp, len(loads), qsrc, qrs, channels, augmented, tensor, ptrs, nimg,
+                pat.ctypes.data_as(C.c_void_p), len(plan), *self.target_shape, *self.patch_size, self.padding_value,
+                torch.cuda.current_stream(device).cuda_stream), "patch_queue_gather_spatial")
         batch = {name: {DATA: outs[name]} for name, _, _ in imgs}
         ini = np.array([p.origin for p in plan], dtype=np.int64)
         batch[LOCATION] = torch.from_numpy(np.hstack([ini, ini + np.array(self.patch_size, dtype=np.int64)]))

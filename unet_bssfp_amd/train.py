@@ -8,6 +8,12 @@ reads ``{"modality": ..., "dirpath": ..., "train": [{image name: NIfTI path, ...
 and trains through two ``data.PatchQueue``s with the reference's arguments; like the reference's ``val_set``
 (src/data_module.py:146-147) the validation queue augments as the training queue does.
 
+``"spatial"`` adds spatial augmentation in front of the reference's transform, for both queues: a list such as
+``[{"type": "RandomFlip", "axes": [0, 1, 2]}, {"type": "RandomAffine", "degrees": 10, "scales": 0.1}]``, every other key
+being a constructor argument of ``augment.RandomFlip`` / ``augment.RandomAffine``.  The ``'dwi-tensor'`` image is reoriented
+with the volume; ``"tensor_rescale"`` -- a 6 x 2 list of per-component (min, max), or the path of a text file that holds one,
+the layout of the reference's ``rescale_args_dwi.txt`` -- says that the tensors are stored normalised.
+
 With ``"stages": ["PRETRAIN", "TRANSFER", "FINE_TUNE"]`` (any sub-list, in order) the manifest runs the thesis's staged
 workflow instead (``train_staged``, stages.py): every stage gets queues of its own modality, starts from the previous stage's
 best checkpoint (the first from ``"ckpt_path"``, if given) and the best paths are printed one per line.  ``"max_epochs"``
@@ -92,6 +98,30 @@ def train_staged(queues, modality: str, dirpath: str, stages: Optional[Sequence]
     return paths
 
 
+def spatial_from_manifest(manifest: Dict) -> Dict:
+    """the ``spatial=`` / ``tensor_images=`` arguments of ``PatchQueue`` from the manifest keys ``"spatial"`` and
+    ``"tensor_rescale"``; ``{}`` when neither is given"""
+    import numpy as np
+    from . import augment
+    kw: Dict = {}
+    if manifest.get("spatial"):
+        kinds = {"RandomFlip": augment.RandomFlip, "RandomAffine": augment.RandomAffine}
+        stages = []
+        for entry in manifest["spatial"]:
+            args = dict(entry)
+            kind = args.pop("type", None)
+            if kind not in kinds:
+                raise ValueError(f'"spatial": unknown type {kind!r} (supported: {sorted(kinds)})')
+            if isinstance(args.get("axes"), list):
+                args["axes"] = tuple(args["axes"])
+            stages.append(kinds[kind](**{k: tuple(v) if isinstance(v, list) else v for k, v in args.items()}))
+        kw["spatial"] = stages
+    if manifest.get("tensor_rescale") is not None:
+        r = manifest["tensor_rescale"]
+        kw["tensor_images"] = {"dwi-tensor": augment.check_tensor_rescale(np.loadtxt(r) if isinstance(r, str) else r)}
+    return kw
+
+
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) != 1:
@@ -105,14 +135,17 @@ def main(argv=None) -> int:
     model_kw = {k: manifest[m] for m, k in (("head", "gen_head"), ("act", "gen_act")) if manifest.get(m) is not None}
     train = [subjects_from_nifti(files, device) for files in manifest["train"]]
     val = [subjects_from_nifti(files, device) for files in manifest["val"]]
+    feed = spatial_from_manifest(manifest)
     if "stages" in manifest:
         epochs = manifest.get("max_epochs", 50)
-        best = train_staged(lambda state, m: (PatchQueue(train, m, seed=seed), PatchQueue(val, m, seed=seed + 1) if val else None),
+        best = train_staged(lambda state, m: (PatchQueue(train, m, seed=seed, **feed),
+                                              PatchQueue(val, m, seed=seed + 1, **feed) if val else None),
                             modality, manifest["dirpath"], stages=manifest["stages"], ckpt_path=manifest.get("ckpt_path"),
                             max_epochs=epochs if isinstance(epochs, dict) else int(epochs), device=device, **model_kw)
         print("\n".join(best))
         return 0
-    best = train_model(PatchQueue(train, modality, seed=seed), PatchQueue(val, modality, seed=seed + 1) if val else None,
+    best = train_model(PatchQueue(train, modality, seed=seed, **feed),
+                       PatchQueue(val, modality, seed=seed + 1, **feed) if val else None,
                        modality, manifest["dirpath"], ckpt_path=manifest.get("ckpt_path"),
                        max_epochs=int(manifest.get("max_epochs", 50)), device=device, **model_kw)
     print(best)
