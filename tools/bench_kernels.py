@@ -138,7 +138,7 @@ def bench_deconv(dtype, reps, only=None):
 
 def bench_wgrad(dtype, reps, only=None):
     cases = [("32->32 @128^3", 32, 32, 128), ("96->32 @128^3", 96, 32, 128), ("64->64 @64^3", 64, 64, 64),
-             ("128->128 @32^3", 128, 128, 32), ("256->256 @16^3", 256, 256, 16), ("512->512 @8^3", 512, 512, 8)]
+             ("128->128 @32^3", 128, 128, 32), ("64->64 @24^3", 64, 64, 24), ("256->256 @16^3", 256, 256, 16), ("512->512 @8^3", 512, 512, 8)]
     for name, cin, cout, s in cases:
         if only and only not in name:
             continue
@@ -175,6 +175,32 @@ def bench_wgrad(dtype, reps, only=None):
         fl = 2.0 * 8 * cp * 8 * cout * n * s ** 3
         nb = (x.numel() + g.numel()) * x.element_size()
         print(f"wgrad     {name:30s} {ms*1e3:9.1f} us  {fl/ms/1e9:8.1f} TFLOP/s (dense)  {nb/ms/1e6:8.1f} GB/s of operands")
+    # the remaining slab writers: the tile form for k2 / k1 (both tile shapes), the transposed-conv classes (wgrad_deconv_kernel at
+    # the wide level, the tile form below it) and wgrad_kernel (strided layers; every 3x3x3 row above under --dtype f32)
+    for name, ks, stride, pad, cin, cout, s in [("k2 tile 64->64 @24^3", 2, 1, 0, 64, 64, 25), ("k2 tile 128->128 @16^3", 2, 1, 0, 128, 128, 17),
+                                                ("k1 tile 64->64 @32^3", 1, 1, 0, 64, 64, 32), ("k1 tile 128->128 @16^3", 1, 1, 0, 128, 128, 16),
+                                                ("k4 s2 generic 32->64 @64^3", 4, 2, 1, 32, 64, 64), ("k3 s2 generic 64->64 @32^3", 3, 2, 1, 64, 64, 32)]:
+        if only and only not in name:
+            continue
+        so = (s + 2 * pad - ks) // stride + 1
+        x = torch.randn(1, s, s, s, cin, device=DEV).to(dtype)
+        g = torch.randn(1, so, so, so, cout, device=DEV).to(dtype)
+        dw = torch.empty(cout, cin, ks, ks, ks, device=DEV)
+        kinds = []
+        ops.WGRAD_PROBE = lambda k, d: kinds.append(k)
+        ms = timeit(lambda: ops.conv_wgrad(x, None, g, (so, so, so), 1, (0, 0, 0), ks, stride, (pad,) * 3, dw, cout, cin, cin * ks ** 3, ks ** 3,
+                                           (ks * ks, ks, 1), (0, 0, 0), (1, 1, 1)), reps)
+        ops.WGRAD_PROBE = None
+        print(f"wgrad     {name:28s} {ms*1e3:9.1f} us  kind {kinds[0]}")
+    for name, cin, cout, s in [("deconv 64->64 @64^3", 64, 64, 64), ("deconv 256->256 @8^3", 256, 256, 8)]:
+        if only and only not in name or dtype != torch.bfloat16:
+            continue
+        x = torch.randn(1, s, s, s, cin, device=DEV).to(dtype)
+        g = torch.randn(1, 2 * s, 2 * s, 2 * s, cout, device=DEV).to(dtype)
+        dw = torch.empty(cin, cout, 2, 2, 2, device=DEV)
+        ms = timeit(lambda: ops.conv_wgrad(x, None, g, (s, s, s), 1, (0, 0, 0), 1, 1, (0, 0, 0), dw, cout, cin, 8, cout * 8, (4, 2, 1), (0, 0, 0),
+                                           (0, 0, 0), g_cls_cout=cout), reps)
+        print(f"wgrad     {name:28s} {ms*1e3:9.1f} us")
 
 
 def bench_norm(dtype, reps, only=None):
