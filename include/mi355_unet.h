@@ -22,6 +22,19 @@
  *    pad channels hold zeros.  `ld` lets a tensor be a channel slice of a wider buffer
  *    (zero-copy skip-concat).  dtype: 0 = f32 (parity mode), 1 = bf16 (throughput mode;
  *    f32 accumulate, f32 statistics, f32 master weights).
+ *
+ * This file is also what the Python binding is made from: unet_bssfp_amd/_lib.py parses it at import and derives every
+ * constant, ctypes.Structure and argtypes list from it, so an ABI change is made here and nowhere else.  It therefore stays
+ * within this C subset (anything else fails the import and names the text; tests/test_abi_host.py):
+ *  - comments in this block form only; the include guard, the `#ifdef __cplusplus` / extern "C" pair, `#include <...>`;
+ *  - `#define MI355_NAME integer`, a negative one as `(-1)`: decimal literals, no expressions, no other macros;
+ *  - `typedef struct tag { ... } name;` whose members are int, int32_t, int64_t, uint64_t, float, double, pointers to
+ *    those, to void, char or uint8_t (any pointer is a c_void_p on the Python side), an earlier struct of this file by
+ *    value, and arrays of these with a literal or MI355_* length; several declarators share a non-pointer type only;
+ *    a new struct also needs its Python name in _lib._STRUCT_NAMES;
+ *  - plain prototypes with named parameters of those types (`(void)` for none), a pointer to a struct of this file, and
+ *    `const char*` as a return type.
+ *  No union, enum, bit-field, function pointer, `unsigned`, size_t, by-value uint8_t or conditional compilation.
  */
 #ifndef MI355_UNET_H
 #define MI355_UNET_H

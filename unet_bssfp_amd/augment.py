@@ -342,7 +342,7 @@ def motion_band_matrix(n_axis: int, first: int, last: int) -> np.ndarray:
 
 # ---- k-space and blur stages: device side ----------------------------------------------------------------------------
 
-AXIS_MAX_N = 128   # MI355_AXIS_MAX_N: the largest extent along an axis that axis_apply takes (larger ones are not tiled)
+AXIS_MAX_N = _lib.H["AXIS_MAX_N"]   # the largest extent along an axis that axis_apply takes (larger ones are not tiled)
 
 
 def _stream():
@@ -533,7 +533,7 @@ class RandomBlur(_Random):
         return x
 
 
-MOTION_MAX_IMAGES = 8   # MI355_MOTION_MAX_IMAGES: K + 1 of one fused launch
+MOTION_MAX_IMAGES = _lib.H["MOTION_MAX_IMAGES"]   # K + 1 of one fused launch
 
 
 def _rigid_rows(matrix) -> np.ndarray:

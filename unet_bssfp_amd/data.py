@@ -36,10 +36,11 @@ import torch
 from . import _lib, augment, nifti
 from .inference import DATA, LOCATION, _triple
 
-_STAGE_KIND = {augment.RandomBiasField: 1, augment.RandomNoise: 2, augment.RandomGamma: 3}   # MI355_STAGE_*
+_STAGE_KIND = {augment.RandomBiasField: _lib.H["STAGE_BIAS_FIELD"], augment.RandomNoise: _lib.H["STAGE_NOISE"],
+               augment.RandomGamma: _lib.H["STAGE_GAMMA"]}
 _NONLOCAL = (augment.RandomMotion, augment.RandomGhosting, augment.RandomSpike, augment.RandomBlur)   # staged, never fused
 _SIGN_PRESERVING = (augment.RandomBiasField, augment.RandomGamma, augment.RandomBlur)      # x >= 0 stays >= 0
-_MAX_IMAGES = 4                                                                              # MI355_QUEUE_MAX_IMAGES
+_MAX_IMAGES = _lib.H["QUEUE_MAX_IMAGES"]
 _SPATIAL = (augment.RandomFlip, augment.RandomAffine)                                        # resampled inside the gather
 
 
@@ -457,8 +458,8 @@ class PatchQueue:
         return q
 
     def gather(self, plan: Sequence[PlannedPatch], out=None, augmented_target: bool = False):
-        """write the patches of ``plan`` (one launch, or one per chunk of MI355_MAX_PATCHES patches / 4 loads): the plain
-        gather, or the spatial one if a load of the plan has a spatial stage with an effect"""
+        """write the patches of ``plan`` (one launch, or one per chunk of MI355_MAX_PATCHES patches / MI355_QUEUE_MAX_LOADS
+        loads, cut by the library): the plain gather, or the spatial one if a load of the plan has a spatial stage with an effect"""
         imgs = self._images(augmented_target)
         sources = {name: [self._by_index[p.load.subject][name][DATA] for p in plan] for _, name, _ in imgs}
         device = self._by_index[plan[0].load.subject][self.modality][DATA].device
