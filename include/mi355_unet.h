@@ -540,6 +540,60 @@ int mi355_dti_errors(const void* pred, const void* target, int32_t dtype, int64_
                      void* workspace, int64_t workspace_bytes, double* table_out, void* const* maps, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Preprocessing (doc/thesis/03-methods.tex:661-685): scanner data -> the network's inputs and targets.
+ *
+ * mi355_dtifit -- log-linear diffusion tensor fit per voxel (FSL DTIFIT's model), ln S_i = ln S0 - b_i g_i^T D g_i:
+ *   design [nmeas][7] f64 rows (-b gx^2, -2b gx gy, -2b gx gz, -b gy^2, -2b gy gz, -b gz^2, 1), pinv [7][nmeas] f64 its
+ *   pseudo-inverse, both in DEVICE memory; unknowns (Dxx, Dxy, Dxz, Dyy, Dyz, Dzz, ln S0) -- the component order of
+ *   src/eval.py:87-92.  7 <= nmeas <= MI355_DTIFIT_MAX_MEAS.  y_i = ln S_i where S_i > 0, else 0 (a NaN signal counts as <= 0).
+ *   MI355_DTIFIT_OLS: beta = pinv y.  MI355_DTIFIT_WLS: weights w_i = S_i^2 (0 where S_i <= 0), the 7 x 7 normal equations
+ *   (28 + 7 sums in registers) solved by Cholesky; a voxel whose factorisation meets a pivot that is not > 0 takes the OLS beta.
+ *   Measurement i of voxel v is read at dwi[i * meas_stride + v * vox_stride] (f32): [N][D][H][W] = (D H W, 1),
+ *   NIfTI (X, Y, Z, N) = (X Y Z, 1) as well, an interleaved series = (1, N).  Tensor component c of voxel v is written at
+ *   tensor[c * out_comp_stride + v * out_vox_stride], elements of out_dtype (MI355_DT_F32 / MI355_DT_F64); s0 (NULL: none):
+ *   [nvox] of out_dtype, exp(beta_7).  norm (NULL: none): HOST array of six (min, max) pairs, which travel by value in the kernel
+ *   arguments; component c is written as (D_c - min_c) / (max_c - min_c), evaluated in f64 before the one rounding of the store.
+ *   mask (NULL: every voxel): uint8 [nvox]; a voxel with mask == 0 gets 0 in every output.  Every output element is written.
+ *   Arithmetic is f64, sums run over the measurements in ascending order.  One lane owns one voxel, or four adjacent ones
+ *   (OLS, vox_stride 1, 16-byte aligned rows); the matrices sit in LDS; no per-voxel storage grows with nmeas.
+ * mi355_channel_minmax -- minmax[ch] = (min(minmax[ch][0], min x[ch]), max(minmax[ch][1], max x[ch])) over the voxels with
+ *   mask != 0 (NULL: all) of a channel-first f32 tensor [c][nvox]; minmax: DEVICE f32 [c][2] that the CALLER initialises to
+ *   (+inf, -inf) and keeps across calls (the dataset loop makes no host read).  Vector integer atomics on the float bits: the
+ *   result does not depend on the order.  NaN values are skipped; -0 counts as +0.
+ * mi355_bssfp_phase_sums -- sums[i] = (Re, Im) of sum_v mag[i][v] exp(j phi[i][v]) in f64, phi = raw / 4095 * 2 pi - pi, for the
+ *   p <= MI355_BSSFP_MAX_CYCLES cycles of two f32 [p][nvox] tensors; two stages in a fixed order (bit-identical calls), the
+ *   partials in workspace (mi355_bssfp_workspace_bytes(p, nvox) bytes, 8-byte aligned); sums: DEVICE double [p][2].
+ * mi355_bssfp_phase_correct -- re, im [p][nvox] f32 = mag cos(phi - theta_i), mag sin(phi - theta_i), theta_i = atan2 of sums[i]
+ *   read from DEVICE memory (the angle never visits the host).
+ * mi355_bssfp_assemble -- out [2p][nvox] f32: channel 2i = (|z_i| - mag_min) / (mag_max - mag_min), channel 2i + 1 =
+ *   (atan2(im_i, re_i) - pha_min) / (pha_max - pha_min), f64 arithmetic, 0 where mask == 0; repeat_cycle >= 0 fills every pair
+ *   from that cycle (the one-bSSFP input), -1 = off.
+ * mi355_normalize_channels -- dst[k][v] = (src[src_channel[k]][v] - ranges[2k]) / (ranges[2k + 1] - ranges[2k]) (f64, one
+ *   rounding), 0 where mask == 0, for k < c_out <= MI355_PREP_MAX_CHANNELS; src [c_src][nvox], dst [c_out][nvox] f32, dst must not
+ *   overlap src; src_channel and ranges are HOST arrays that travel by value.  T1w: one source channel repeated 6 times.
+ * All: caller-owned device pointers, launches on `stream` only, no sync, no allocation; bad arguments return MI355_ERR_ARG
+ * before any launch.
+ * ---------------------------------------------------------------------------------------- */
+#define MI355_DTIFIT_MAX_MEAS 512
+#define MI355_DTIFIT_OLS 0
+#define MI355_DTIFIT_WLS 1
+#define MI355_BSSFP_MAX_CYCLES 16
+#define MI355_PREP_MAX_CHANNELS 32
+int mi355_dtifit(const float* dwi, int64_t nvox, int32_t nmeas, int64_t meas_stride, int64_t vox_stride, const double* design,
+                 const double* pinv, int32_t method, const uint8_t* mask, void* tensor, int32_t out_dtype,
+                 int64_t out_comp_stride, int64_t out_vox_stride, void* s0, const double* norm, void* stream);
+int mi355_channel_minmax(const float* x, int32_t c, int64_t nvox, const uint8_t* mask, float* minmax, void* stream);
+int64_t mi355_bssfp_workspace_bytes(int32_t p, int64_t nvox);
+int mi355_bssfp_phase_sums(const float* mag, const float* phase_raw, int32_t p, int64_t nvox, void* workspace,
+                           int64_t workspace_bytes, double* sums, void* stream);
+int mi355_bssfp_phase_correct(const float* mag, const float* phase_raw, int32_t p, int64_t nvox, const double* sums, float* re,
+                              float* im, void* stream);
+int mi355_bssfp_assemble(const float* re, const float* im, int32_t p, int64_t nvox, const uint8_t* mask, double mag_min,
+                         double mag_max, double pha_min, double pha_max, int32_t repeat_cycle, float* out, void* stream);
+int mi355_normalize_channels(const float* src, int32_t c_src, const int32_t* src_channel, const double* ranges, int32_t c_out,
+                             int64_t nvox, const uint8_t* mask, float* dst, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sliding-window inference -- the data movement of `predict_step` /
  * `test_step` (src/model.py:291-333) around Generator.forward: TorchIO's GridSampler patch
  * extraction and GridAggregator.add_batch / get_output_tensor (src/data_module.py:168-183).
