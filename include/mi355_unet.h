@@ -594,6 +594,34 @@ int mi355_normalize_channels(const float* src, int32_t c_src, const int32_t* src
                              int64_t nvox, const uint8_t* mask, float* dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Regridding onto another voxel grid (csrc/regrid_core.h states the arithmetic): a [c][sd][sh][sw] source is
+ * read through a 3 x 4 index matrix m (row-major f64, a HOST array that travels by value in the kernel arguments) into a
+ * [c][od][oh][ow] f32 output.  Output voxel (i_D, i_H, i_W) reads the source at s_a = m[4a] i_D + m[4a+1] i_H + m[4a+2] i_W +
+ * m[4a+3], three f64 fmas per axis; inside iff -0.5 <= s_a < N_a - 0.5 on every axis, an outside voxel gets `fill` (one value
+ * for all channels).
+ *   mi355_regrid            : order MI355_REGRID_NEAREST (tap floor(s + 0.5)) and MI355_REGRID_LINEAR (taps floor(s),
+ *                             floor(s) + 1) read f32 samples with taps clamped into the volume; MI355_REGRID_CUBIC reads f64
+ *                             cubic B-spline COEFFICIENTS (mi355_bspline_prefilter) at the four taps floor(s) - 1 .. floor(s) + 2
+ *                             per axis, mirrored about the centres of the edge voxels (scipy's mode='mirror').  The sum runs in
+ *                             f64 in a fixed order (axis D outermost, taps ascending) and is rounded once at the store.  Every
+ *                             output element is written; out must not overlap src; extents 1 .. 4096.
+ *   mi355_bspline_prefilter : f32 samples x [c][d][h][w] -> f64 coefficients coef of the same shape, out of place: the
+ *                             separable recursion with pole sqrt(3) - 2 and the exact mirror start along W, H and D in that
+ *                             order, three launches for all channels.  Every coefficient is written.  Extents 1 ..
+ *                             MI355_REGRID_MAX_N per axis (a line is not tiled); a larger one returns MI355_ERR_UNSUPPORTED
+ *                             before any launch (c d h above 2^31 - 1: MI355_ERR_ARG).  An axis of extent 1 is left as it is.
+ * Both: caller-owned device pointers, launches on `stream` only, no atomics, no workspace, no sync; bad arguments return
+ * MI355_ERR_ARG before any launch.
+ * ---------------------------------------------------------------------------------------- */
+#define MI355_REGRID_MAX_N 512
+#define MI355_REGRID_NEAREST 0
+#define MI355_REGRID_LINEAR 1
+#define MI355_REGRID_CUBIC 3
+int mi355_bspline_prefilter(const float* x, double* coef, int32_t c, int32_t d, int32_t h, int32_t w, void* stream);
+int mi355_regrid(const void* src, float* out, int32_t c, int32_t sd, int32_t sh, int32_t sw, int32_t od, int32_t oh, int32_t ow,
+                 const double* m, int32_t order, float fill, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sliding-window inference -- the data movement of `predict_step` /
  * `test_step` (src/model.py:291-333) around Generator.forward: TorchIO's GridSampler patch
  * extraction and GridAggregator.add_batch / get_output_tensor (src/data_module.py:168-183).

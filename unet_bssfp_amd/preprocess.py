@@ -8,9 +8,16 @@ The thesis builds every input and target from scanner data (doc/thesis/03-method
   the diagonal and the off-diagonal elements as separate groups -- ``gradient_table`` + ``fit_tensor``;
 * phase-cycled bSSFP: scanner phase [0, 4095] -> [-pi, pi], every cycle rotated by exp(-j angle(sum_xyz complex_i)), then
   magnitude and phase, each normalised to [0, 1] over the dataset and interleaved -- ``phase_correct`` + ``assemble_bssfp``
-  (``repeat_cycle`` gives the one-bSSFP input).  Gibbs removal and resampling sit between the two calls in the thesis; they are
-  not part of this module, the caller runs them on (re, im) if wanted;
+  (``repeat_cycle`` gives the one-bSSFP input).  Gibbs removal and resampling sit between the two calls in the thesis:
+  resampling is ``regrid`` (below; the pipeline runs it on (re, im) with the ``regrid`` option), Gibbs removal is not part of
+  this module, the caller runs it on (re, im) if wanted;
 * T1w: masked, normalised to [0, 1], repeated to 6 channels -- ``assemble_t1w``.
+
+Files of one subject need not share a grid: ``index_matrix`` turns two NIfTI affines and an optional
+co-registration matrix into the voxel-to-voxel matrix, ``regrid`` resamples a volume through it on the device with nearest,
+linear or cubic B-spline interpolation (``bspline_coefficients`` is the prefilter), and ``preprocess_subject(regrid=...)`` /
+the manifest key ``"regrid"`` bring mask, T1w and bSSFP onto the DWI grid.  The B-spline path is pinned against
+``scipy.ndimage`` (``mode='mirror'``); parity with SPM's or FSL's reslicing is not pinned.
 
 ``RangeAccumulator`` gathers the dataset ranges on the device (one host read at the end), ``preprocess_subject`` goes from files
 to files, and the command line runs the two passes (ranges, then outputs) over a manifest.
@@ -375,6 +382,91 @@ def normalize_tensor(t: torch.Tensor, ranges, mask: Optional[torch.Tensor] = Non
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# regridding onto a common grid
+# ----------------------------------------------------------------------------------------------------------------------
+MAX_SPLINE_EXTENT = _lib.H["REGRID_MAX_N"]
+_ORDERS = {"nearest": _lib.H["REGRID_NEAREST"], "linear": _lib.H["REGRID_LINEAR"], "bspline": _lib.H["REGRID_CUBIC"]}
+
+
+def _affine(a, what: str) -> np.ndarray:
+    a = np.asarray(a, dtype=np.float64)
+    if a.shape != (4, 4) or not np.all(np.isfinite(a)):
+        raise ValueError(f"{what}: expected a finite 4 x 4 matrix, got shape {a.shape}")
+    s = np.linalg.svd(a[:3, :3], compute_uv=False)
+    if not s[-1] > 1e-12 * s[0]:
+        raise ValueError(f"{what}: the matrix is singular (singular values {s})")
+    return a
+
+
+def index_matrix(src_affine, dst_affine, xfm=None) -> np.ndarray:
+    """The (3, 4) f64 matrix that carries a voxel index of the destination grid to the continuous voxel index of the source
+    image: ``inv(src_affine) @ xfm @ dst_affine``.  The affines are NIfTI voxel-to-world matrices; ``xfm`` (default: identity)
+    is a 4 x 4 world-to-world matrix from destination-grid world coordinates to source-image world coordinates, which is what
+    a co-registration returns.  Tensor axes (D, H, W) are the NIfTI array axes (X, Y, Z).  A singular matrix raises."""
+    src, dst = _affine(src_affine, "index_matrix: src_affine"), _affine(dst_affine, "index_matrix: dst_affine")
+    x = np.eye(4) if xfm is None else _affine(xfm, "index_matrix: xfm")
+    return np.ascontiguousarray((np.linalg.inv(src) @ x @ dst)[:3])
+
+
+def _volume(what: str, x: torch.Tensor, dtype) -> torch.Tensor:
+    if x.dim() != 4 or x.dtype != dtype or min(x.shape) < 1:
+        raise ValueError(f"{what}: expected a non-empty (C, D, H, W) {dtype} tensor, got {x.dtype} {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def bspline_coefficients(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(C, D, H, W) float32 samples -> float64 cubic B-spline coefficients of the same shape (the separable prefilter with
+    mirror boundaries, ``scipy.ndimage.spline_filter(order=3, mode='mirror')``): what ``regrid(..., "bspline")`` reads.  A
+    caller that regrids one volume several times computes them once.  Extents up to 512 per axis."""
+    _require_cuda("bspline_coefficients", x=x, out=out)
+    x = _volume("bspline_coefficients", x, torch.float32)
+    coef = _out(out, x.shape, torch.float64, x.device, "bspline_coefficients")
+    _lib.check(_lib.load().mi355_bspline_prefilter(x.data_ptr(), coef.data_ptr(), *x.shape, _stream(x)), "bspline_prefilter")
+    return coef
+
+
+def regrid(x: torch.Tensor, matrix, out_shape, interpolation: str = "linear", fill: float = 0.0,
+           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Resample a (C, D, H, W) float32 device tensor onto a grid of ``out_shape`` = (D', H', W'): output voxel i reads the
+    source at the continuous index ``matrix @ (i, 1)`` (``index_matrix``; (3, 4) or (4, 4), f64 on the device too).  Inside
+    ``-0.5 <= s < N - 0.5`` the value is interpolated -- ``"nearest"``, ``"linear"`` (taps clamped into the volume) or
+    ``"bspline"`` (cubic, mirror boundaries) -- outside it is ``fill``.  With ``"bspline"`` a float64 ``x`` is taken as the
+    coefficients of ``bspline_coefficients``; a float32 ``x`` is prefiltered first.  Returns (C, D', H', W') float32."""
+    if interpolation not in _ORDERS:
+        raise ValueError(f"interpolation must be one of {sorted(_ORDERS)}, got {interpolation!r}")
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape not in ((3, 4), (4, 4)) or not np.all(np.isfinite(m)):
+        raise ValueError(f"regrid: matrix must be a finite (3, 4) or (4, 4) array, got shape {m.shape}")
+    out_shape = tuple(int(n) for n in out_shape)
+    if len(out_shape) != 3 or min(out_shape) < 1:
+        raise ValueError(f"regrid: out_shape must be three positive extents, got {out_shape}")
+    _require_cuda("regrid", x=x, out=out)
+    if interpolation == "bspline" and x.dtype == torch.float64:
+        src = _volume("regrid", x, torch.float64)
+    else:
+        src = _volume("regrid", x, torch.float32)
+        if interpolation == "bspline":
+            src = bspline_coefficients(src)
+    res = _out(out, (src.shape[0],) + out_shape, torch.float32, src.device, "regrid")
+    _lib.check(_lib.load().mi355_regrid(src.data_ptr(), res.data_ptr(), *src.shape, *out_shape,
+                                        (C.c_double * 12)(*m[:3].reshape(-1)), _ORDERS[interpolation], float(fill),
+                                        _stream(src)), "regrid")
+    return res
+
+
+def _regrid_options(regrid_opts) -> Optional[Tuple[str, float]]:
+    if regrid_opts is None:
+        return None
+    unknown = set(regrid_opts) - {"interpolation", "fill"}
+    if unknown:
+        raise ValueError(f"regrid: unknown options {sorted(unknown)}; the keys are 'interpolation' and 'fill'")
+    interpolation = regrid_opts.get("interpolation", "linear")
+    if interpolation not in _ORDERS:
+        raise ValueError(f"regrid: interpolation must be one of {sorted(_ORDERS)}, got {interpolation!r}")
+    return interpolation, float(regrid_opts.get("fill", 0.0))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # files to files
 # ----------------------------------------------------------------------------------------------------------------------
 OUTPUTS = {"dwi-tensor": "desc-normtensor_dwi", "pc-bssfp": "desc-normflatbet_pc-bssfp", "bssfp": "desc-normflatbet_bssfp",
@@ -382,8 +474,13 @@ OUTPUTS = {"dwi-tensor": "desc-normtensor_dwi", "pc-bssfp": "desc-normflatbet_pc
 RANGE_KEYS = ("dwi-tensor", "bssfp-mag", "bssfp-phase", "t1w")
 
 
-def _load_subject(files: Dict[str, str], device):
-    """raw device tensors of one subject: dwi (X, Y, Z, N), mask (X, Y, Z) u8, mag / phase (P, X, Y, Z), t1 (X, Y, Z)"""
+def _load_subject(files: Dict[str, str], device, regrid_opts=None):
+    """raw device tensors of one subject: dwi (X, Y, Z, N), mask (X, Y, Z) u8, mag / phase (P, X, Y, Z), t1 (X, Y, Z).
+    ``regrid_opts`` = (interpolation, fill): mask and t1 arrive on the DWI grid, mag / phase stay on their own and
+    ``bssfp_matrix`` says how to bring the corrected series over (``_corrected_bssfp``)."""
+    if regrid_opts is not None:
+        return _load_on_dwi_grid(files, device, *regrid_opts)
+
     def vol(key):
         return torch.from_numpy(np.ascontiguousarray(nifti.load(files[key])[0], dtype=np.float32)).to(device)
     sub = {"dwi": vol("dwi"), "mask": (vol("mask") != 0).to(torch.uint8)}
@@ -395,19 +492,65 @@ def _load_subject(files: Dict[str, str], device):
     return sub
 
 
+def _load_on_dwi_grid(files: Dict[str, str], device, interpolation: str, fill: float):
+    """The DWI file's (shape, affine) is the common grid.  A file is regridded when its shape or its affine differs from the
+    DWI's, or when ``files["xfm"][key]`` names a 4 x 4 text matrix (destination world -> source world; key ``bssfp_mag``
+    stands for the series, whose phase file shares the magnitude's grid).  The mask always takes "nearest" and fill 0."""
+    def vol(key):
+        data, affine = nifti.load(files[key])
+        return torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)).to(device), affine
+    dwi, grid_affine = vol("dwi")
+    grid, xfms = tuple(dwi.shape[:3]), files.get("xfm", {})
+
+    def matrix(key, t, affine):                                # None: the file already sits on the DWI grid
+        if key not in xfms and tuple(t.shape[:3]) == grid and np.allclose(affine, grid_affine, rtol=0, atol=1e-5):
+            return None
+        return index_matrix(affine, grid_affine, np.loadtxt(xfms[key], dtype=np.float64, ndmin=2) if key in xfms else None)
+
+    mask, affine = vol("mask")
+    m = matrix("mask", mask, affine)
+    mask = (mask != 0).to(torch.float32)
+    sub = {"dwi": dwi, "mask": ((mask if m is None else regrid(mask[None], m, grid, "nearest", 0.0)[0]) != 0).to(torch.uint8)}
+    if "bssfp_mag" in files:
+        (mag, affine), (phase, phase_affine) = vol("bssfp_mag"), vol("bssfp_phase")
+        if phase.shape != mag.shape or not np.allclose(phase_affine, affine, rtol=0, atol=1e-5):
+            raise ValueError(f"bssfp_phase {tuple(phase.shape)} does not sit on the grid of bssfp_mag {tuple(mag.shape)}: "
+                             "the shapes or the affines differ")
+        sub["mag"], sub["phase"] = mag.movedim(-1, 0).contiguous(), phase.movedim(-1, 0).contiguous()
+        sub["bssfp_matrix"] = matrix("bssfp_mag", mag, affine)
+    if "t1w" in files:
+        t1, affine = vol("t1w")
+        m = matrix("t1w", t1, affine)
+        sub["t1"] = t1 if m is None else regrid(t1[None], m, grid, interpolation, fill)[0]
+    return sub
+
+
+def _corrected_bssfp(sub, regrid_opts):
+    """(re, im) of the phase-corrected series.  The correction runs on the series' NATIVE grid and the real and imaginary
+    parts are regridded: a wrapped phase is never interpolated."""
+    re, im = phase_correct(sub["mag"], sub["phase"])
+    m = sub.get("bssfp_matrix")
+    if m is not None:
+        grid, (interpolation, fill) = tuple(sub["dwi"].shape[:3]), regrid_opts
+        re, im = regrid(re, m, grid, interpolation, fill), regrid(im, m, grid, interpolation, fill)
+    return re, im
+
+
 def _table_of(files, table):
     return table if table is not None else gradient_table(files["bval"], files["bvec"])
 
 
 def accumulate_subject(files: Dict[str, str], accumulators: Dict[str, RangeAccumulator], table: Optional[GradientTable] = None,
-                       method: str = "ols", device="cuda:0") -> None:
+                       method: str = "ols", device="cuda:0", regrid: Optional[Dict[str, object]] = None) -> None:
     """First pass: folds one subject's raw tensor, bSSFP magnitude / phase and T1w values inside the mask into
-    ``accumulators`` (made by ``make_accumulators``).  No host read."""
-    sub = _load_subject(files, device)
+    ``accumulators`` (made by ``make_accumulators``).  No host read.  ``regrid``: as in ``preprocess_subject``; the ranges are
+    then those of the regridded values, the ones the second pass normalises."""
+    opts = _regrid_options(regrid)
+    sub = _load_subject(files, device, opts)
     tensor = fit_tensor(sub["dwi"], _table_of(files, table), method, sub["mask"], channels_first=False)
     accumulators["dwi-tensor"].update(tensor, sub["mask"])
     if "mag" in sub:
-        re, im = phase_correct(sub["mag"], sub["phase"])
+        re, im = _corrected_bssfp(sub, opts)
         accumulators["pc-bssfp"].update(assemble_bssfp(re, im, sub["mask"], (0.0, 1.0), (0.0, 1.0)), sub["mask"])
     if "t1" in sub:
         accumulators["t1w"].update(sub["t1"][None], sub["mask"])
@@ -439,13 +582,20 @@ def ranges_of(accumulators: Dict[str, RangeAccumulator]) -> Dict[str, object]:
 
 
 def preprocess_subject(files: Dict[str, str], ranges: Dict[str, object], out_dir: str, table: Optional[GradientTable] = None,
-                       method: str = "ols", device="cuda:0", one_bssfp_cycle: int = 0) -> Dict[str, str]:
+                       method: str = "ols", device="cuda:0", one_bssfp_cycle: int = 0,
+                       regrid: Optional[Dict[str, object]] = None) -> Dict[str, str]:
     """Second pass, files to files.  ``files``: ``dwi`` (X, Y, Z, N), ``bval`` / ``bvec`` (FSL text; or pass ``table``),
     ``mask`` (X, Y, Z), optionally ``bssfp_mag`` + ``bssfp_phase`` (X, Y, Z, P; phase in scanner units) and ``t1w`` (X, Y, Z),
     and the labels ``sub`` / ``ses`` of the file names.  ``ranges``: ``ranges_of(...)``.  Writes (X, Y, Z, C) float32 NIfTI
     files -- ``dwi-tensor`` (6 channels), ``pc-bssfp`` (2P), ``bssfp`` (cycle ``one_bssfp_cycle`` repeated, 2P) and ``t1w`` (6) --
-    and returns ``{image name: path}``, an entry of the ``train`` / ``val`` lists that ``data.subjects_from_nifti`` reads."""
-    sub = _load_subject(files, device)
+    and returns ``{image name: path}``, an entry of the ``train`` / ``val`` lists that ``data.subjects_from_nifti`` reads.
+    ``regrid`` = ``{"interpolation": "linear" | "bspline" | "nearest", "fill": 0.0}`` (default None: every file must already sit
+    on the DWI grid): the DWI file's shape and affine are the common grid, and ``mask`` (always "nearest"), ``t1w`` and the
+    bSSFP series are regridded onto it where their shape or affine differs or ``files["xfm"][key]`` names a 4 x 4 text matrix
+    (DWI-grid world -> that file's world, as a co-registration returns it; key ``bssfp_mag`` for the series).  The series is
+    phase-corrected on its own grid, then (re, im) are regridded.  The DWI series itself is never regridded."""
+    opts = _regrid_options(regrid)
+    sub = _load_subject(files, device, opts)
     os.makedirs(out_dir, exist_ok=True)
     stem = os.path.join(out_dir, f"sub-{files.get('sub', 'unknown')}_ses-{files.get('ses', 'unknown')}_")
     affine = nifti.load(files["dwi"])[1]
@@ -458,7 +608,7 @@ def preprocess_subject(files: Dict[str, str], ranges: Dict[str, object], out_dir
     write("dwi-tensor", fit_tensor(sub["dwi"], _table_of(files, table), method, sub["mask"], norm=ranges["dwi-tensor"],
                                    channels_first=False))
     if "mag" in sub:
-        re, im = phase_correct(sub["mag"], sub["phase"])
+        re, im = _corrected_bssfp(sub, opts)
         write("pc-bssfp", assemble_bssfp(re, im, sub["mask"], ranges["bssfp-mag"], ranges["bssfp-phase"]))
         write("bssfp", assemble_bssfp(re, im, sub["mask"], ranges["bssfp-mag"], ranges["bssfp-phase"], repeat_cycle=one_bssfp_cycle))
     if "t1" in sub:
@@ -468,7 +618,8 @@ def preprocess_subject(files: Dict[str, str], ranges: Dict[str, object], out_dir
 
 def main(argv=None) -> int:
     """manifest.json: ``{"subjects": [files, ...], "out_dir": ..., "method": "ols", "device": "cuda:0", "val": [indices],
-    "cycles": 12}`` (``files`` as in ``preprocess_subject``; only the first two keys are required).
+    "cycles": 12, "regrid": {"interpolation": "linear", "fill": 0.0}}`` (``files`` and ``regrid`` as in ``preprocess_subject``;
+    only the first two keys are required).
     Pass 1 gathers the dataset ranges, pass 2 writes the volumes.  Leaves ``rescale_args_<key>.txt`` per range and
     ``train_manifest.json`` with the ``train`` / ``val`` / ``tensor_rescale`` keys of ``python -m unet_bssfp_amd.train``."""
     argv = sys.argv[1:] if argv is None else argv
@@ -478,6 +629,7 @@ def main(argv=None) -> int:
     with open(argv[0]) as f:
         manifest = json.load(f)
     device, method, out_dir = manifest.get("device", "cuda:0"), manifest.get("method", "ols"), manifest["out_dir"]
+    regrid_opts = manifest.get("regrid")
     subjects = manifest["subjects"]
     os.makedirs(out_dir, exist_ok=True)
     cycles = manifest.get("cycles")                          # phase cycles per bSSFP series; default: the first series'
@@ -487,11 +639,11 @@ def main(argv=None) -> int:
     acc = make_accumulators(cycles, device)
     tables = [gradient_table(s["bval"], s["bvec"]) for s in subjects]
     for s, t in zip(subjects, tables):
-        accumulate_subject(s, acc, t, method, device)
+        accumulate_subject(s, acc, t, method, device, regrid_opts)
     ranges = ranges_of(acc)
     for key in ranges:
         write_rescale_args(os.path.join(out_dir, f"rescale_args_{key}.txt"), ranges[key])
-    entries = [preprocess_subject(s, ranges, out_dir, t, method, device) for s, t in zip(subjects, tables)]
+    entries = [preprocess_subject(s, ranges, out_dir, t, method, device, regrid=regrid_opts) for s, t in zip(subjects, tables)]
     val = set(manifest.get("val", ()))
     out = {"train": [e for i, e in enumerate(entries) if i not in val], "val": [e for i, e in enumerate(entries) if i in val],
            "tensor_rescale": ranges["dwi-tensor"].tolist()}
