@@ -257,7 +257,8 @@ def _normact_case(kind, n, c, sp, dtype, p, small=False, s2d_out=False, bn_group
         rm, rv = (rnd(c), rnd(c, lo=0.5)) if bn else (None, None)
         nbt = torch.zeros((), dtype=torch.long, device=DEV) if bn else None
         cfg = Fn.NormCfg(kind, c, slope=0.1 if kind == "instance" else 0.2, p=p)
-        a = Fn.NormActFn.apply(z, None, gamma, beta, None, cfg, training, rm, rv, s2d_out, nbt, small, bn_groups)
+        a = Fn.NormActFn.apply(z, None, gamma, beta, None, None, rm, rv, nbt, cfg, training,
+                               Fn.NormOpts(s2d_out=s2d_out, small=small, bn_groups=bn_groups))
         ga = rnd(n, c, *sp)
         a.backward(s2d(ga, dtype, z.shape[4]) if s2d_out else act(ga, dtype))
         out = {"a": a, "dz": z.grad}
@@ -306,7 +307,7 @@ def _normact_pool_case(dtype, p, with_skip):
         z = act(rndn(n, c, *sp, scale=1.5, shift=0.3), dtype).requires_grad_(True)
         gamma, beta = rnd(c, lo=0.5).requires_grad_(True), rnd(c).requires_grad_(True)
         cfg = Fn.NormCfg("instance", c, slope=0.1, p=p)
-        a = Fn.NormActFn.apply(z, None, gamma, beta, None, cfg, True, None, None, False, None, False, 1, None, None, None, True)
+        a = Fn.NormActFn.apply(z, None, gamma, beta, None, None, None, None, None, cfg, True, Fn.NormOpts(pool_after=True))
         assert Fn.PoolSide._by_ptr, "the fused pool did not run"
         skip, pooled = Fn.SkipPoolFn.apply_to(a)
         dy = act(rndn(n, c, *(e // 2 for e in sp)), dtype)
@@ -339,7 +340,7 @@ def _normact_final_case(p, skip_a):
         cfg = Fn.NormCfg("instance", c, slope=0.1, p=p)
         spec = Fn.ConvSpec("conv", c, k, 1, 1, 0)
         with torch.set_grad_enabled(not skip_a):
-            a = Fn.NormActFn.apply(z, None, gamma, beta, None, cfg, True, None, None, False, None, False, 1, None, None, (w, b, skip_a))
+            a = Fn.NormActFn.apply(z, None, gamma, beta, None, None, None, None, None, cfg, True, Fn.NormOpts(final=(w, b, skip_a)))
             y, _ = Fn.ConvFn.apply(a, None, w, b, spec, False, False, 0, False, True)
         if skip_a:
             # contract region: with skip_a the activation itself is not written, its only consumer is the fused convolution
@@ -449,7 +450,7 @@ def _fp8_ops():
     z = act(rndn(n, c, *sp, scale=1.5, shift=0.3), BF16).requires_grad_(True)
     gamma, beta = rnd(c, lo=0.5).requires_grad_(True), rnd(c).requires_grad_(True)
     cfg = Fn.NormCfg("instance", c, slope=0.1, p=0.1)
-    a = Fn.NormActFn.apply(z, None, gamma, beta, None, cfg, True, None, None, False, None, False, 1, sa, sg)
+    a = Fn.NormActFn.apply(z, None, gamma, beta, None, None, None, None, None, cfg, True, Fn.NormOpts(emit8=sa, emit8_bwd=sg))
     a8 = Fn.Fp8Side.take(a)[0]
     a.backward(act(rnd(n, c, *sp), BF16))
     (dz8, _, dz), = Fn.Fp8Side._by_ptr.values()                # (the copy travels under the tensor the backward kernel wrote)

@@ -309,10 +309,10 @@ def test_normact_fwd_bwd(hip, dtype, kind, n, c, sp):
     gd, bd = gamma.to(DEV).requires_grad_(True), beta.to(DEV).requires_grad_(True)
     rmd, rvd = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
     if kind == "none":
-        a = Fn.NormActFn.apply(zd, None, None, None, None, cfg, True, None, None)
+        a = Fn.NormActFn.apply(zd, None, None, None, None, None, None, None, None, cfg, True)
     else:
-        a = Fn.NormActFn.apply(zd, None, gd, bd, None, cfg, True, rmd if kind == "batch" else None,
-                               rvd if kind == "batch" else None)
+        a = Fn.NormActFn.apply(zd, None, gd, bd, None, None, rmd if kind == "batch" else None,
+                               rvd if kind == "batch" else None, None, cfg, True)
     close(from_act(a, c), a_ref.detach(), dtype, "a")
     a.backward(to_act(ga, dtype))
     if dtype == torch.float32:
@@ -363,8 +363,8 @@ def test_normact_small_tensor_kernels(hip, dtype, kind, n, c, sp, s2d):
         rmd, rvd = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
         nbt = torch.zeros((), dtype=torch.long, device=DEV)
         bn = kind == "batch"
-        a = Fn.NormActFn.apply(zd, None, gd, bd, None, cfg, True, rmd if bn else None, rvd if bn else None, s2d,
-                               nbt if bn else None, small)
+        a = Fn.NormActFn.apply(zd, None, gd, bd, None, None, rmd if bn else None, rvd if bn else None, nbt if bn else None,
+                               cfg, True, Fn.NormOpts(s2d_out=s2d, small=small))
         if s2d:                                              # S(a) back to the plain layout; the gradient arrives in S layout
             a_plain = ops.unpack_ncdhw_s2d(a.detach(), c, sp, c, 0).cpu()
             gs = Fn._new_s2d(ops.s2d_shape(n, *sp, c), dtype, DEV)
@@ -415,8 +415,8 @@ def test_normact_small_resident_forms_equal_the_three_launch_path_with_dropout(h
         gd, bd = gamma.to(DEV).requires_grad_(True), beta.to(DEV).requires_grad_(True)
         rmd, rvd = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
         nbt = torch.zeros((), dtype=torch.long, device=DEV)
-        a = Fn.NormActFn.apply(zd, None, gd, bd, None, cfg, True, rmd if bn else None, rvd if bn else None, False,
-                               nbt if bn else None, small, bn_groups)
+        a = Fn.NormActFn.apply(zd, None, gd, bd, None, None, rmd if bn else None, rvd if bn else None, nbt if bn else None,
+                               cfg, True, Fn.NormOpts(small=small, bn_groups=bn_groups))
         a.backward(to_act(ga, dtype))
         outs[small] = (from_act(a.detach(), c), from_act(zd.grad, c), gd.grad.cpu(), bd.grad.cpu(), rmd.cpu(), rvd.cpu(), int(nbt))
     sm, big = outs[True], outs[False]
@@ -476,7 +476,7 @@ def test_batchnorm_eval_mode(hip, dtype):
     cfg = Fn.NormCfg("batch", c, slope=0.2)
     zd = to_act(z, dtype).requires_grad_(True)
     rmd, rvd = rm.to(DEV), rv.to(DEV)
-    a = Fn.NormActFn.apply(zd, None, gamma.to(DEV), beta.to(DEV), None, cfg, False, rmd, rvd)
+    a = Fn.NormActFn.apply(zd, None, gamma.to(DEV), beta.to(DEV), None, None, rmd, rvd, None, cfg, False)
     close(from_act(a, c), a_ref.detach(), dtype, "a")
     a.backward(to_act(ga, dtype))
     close(from_act(zd.grad, c), z_cpu.grad, dtype, "dz")
@@ -488,8 +488,8 @@ def test_norm_single_value_raises(hip):
     z = to_act(torch.rand(1, 32, 1, 1, 1), torch.float32)
     cfg = Fn.NormCfg("batch", 32, slope=0.2)
     with pytest.raises(ValueError):
-        Fn.NormActFn.apply(z, None, torch.ones(32, device=DEV), torch.zeros(32, device=DEV), None, cfg, True,
-                           torch.zeros(32, device=DEV), torch.ones(32, device=DEV))
+        Fn.NormActFn.apply(z, None, torch.ones(32, device=DEV), torch.zeros(32, device=DEV), None, None,
+                           torch.zeros(32, device=DEV), torch.ones(32, device=DEV), None, cfg, True)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -501,7 +501,7 @@ def test_dropout_statistics_and_backward_mask(hip, dtype):
     cfg = Fn.NormCfg("instance", c, slope=0.1, p=p)
     zd = to_act(z, dtype).requires_grad_(True)
     ones, zeros = torch.ones(c, device=DEV), torch.zeros(c, device=DEV)
-    a = Fn.NormActFn.apply(zd, None, ones, zeros, None, cfg, True, None, None)
+    a = Fn.NormActFn.apply(zd, None, ones, zeros, None, None, None, None, None, cfg, True)
     av = from_act(a, c)
     dropped = (av == 0).float().mean().item()
     assert abs(dropped - p) < 0.004                       # ~131k elements: sigma ~ 6e-4
@@ -509,7 +509,7 @@ def test_dropout_statistics_and_backward_mask(hip, dtype):
     keep = av != 0
     close(av[keep], ref[keep], dtype, "kept")
     # eval mode: no dropout
-    a_eval = Fn.NormActFn.apply(zd, None, ones, zeros, None, cfg, False, None, None)
+    a_eval = Fn.NormActFn.apply(zd, None, ones, zeros, None, None, None, None, None, cfg, False)
     close(from_act(a_eval, c), ref * (1 - p), dtype, "eval")
     # backward uses the same mask: dz is exactly 0-contribution where dropped => check via linearity
     a.backward(to_act(torch.ones(1, c, 16, 16, 16), dtype))
@@ -719,8 +719,8 @@ def test_normact_writes_and_reads_s2d(hip, dtype):
     mk = lambda: (torch.zeros(c, device=DEV), torch.ones(c, device=DEV))
     rm1, rv1 = mk()
     rm2, rv2 = mk()
-    a_plain = Fn.NormActFn.apply(zd1, None, gamma.to(DEV), beta.to(DEV), None, cfg, True, rm1, rv1, False)
-    a_s2d = Fn.NormActFn.apply(zd2, None, gamma.to(DEV), beta.to(DEV), None, cfg, True, rm2, rv2, True)
+    a_plain = Fn.NormActFn.apply(zd1, None, gamma.to(DEV), beta.to(DEV), None, None, rm1, rv1, None, cfg, True)
+    a_s2d = Fn.NormActFn.apply(zd2, None, gamma.to(DEV), beta.to(DEV), None, None, rm2, rv2, None, cfg, True, Fn.NormOpts(s2d_out=True))
     assert a_s2d.shape == (n, 3, 5, 5, 8 * c)
     ref = to_s2d(from_act(a_plain, c), dtype, c)
     assert torch.equal(a_s2d.float().cpu(), ref.float().cpu())
@@ -1060,7 +1060,7 @@ def _norm_backward_forms_the_maxpool_gradient_itself(dtype, drop_p, levels):
             Fn.DropoutState._salt = 0
             zz = z.clone().requires_grad_(True)
             gg, bb = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
-            act = Fn.NormActFn.apply(zz, None, gg, bb, None, cfg, True, None, None, False, None, False, 1, None, None, None, True)
+            act = Fn.NormActFn.apply(zz, None, gg, bb, None, None, None, None, None, cfg, True, Fn.NormOpts(pool_after=True))
             assert bool(Fn.PoolSide._by_ptr) == lazy
             skip, pooled = Fn.SkipPoolFn.apply_to(act)
             torch.autograd.backward([skip, pooled], [wide[..., c:], dy])
@@ -1131,7 +1131,7 @@ def test_norm_backward_forms_the_final_convs_data_gradient_itself(hip, drop_p):
         zz = z.clone().requires_grad_(True)
         gg, bb, ww = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True), w.clone().requires_grad_(True)
         fin = (ww, bias, False) if lazy else None            # lazy: forward fused as well (Fn.FusedFinal)
-        a = Fn.NormActFn.apply(zz, None, gg, bb, None, cfg, True, None, None, False, None, False, 1, None, None, fin)
+        a = Fn.NormActFn.apply(zz, None, gg, bb, None, None, None, None, None, cfg, True, Fn.NormOpts(final=fin))
         y, _ = Fn.ConvFn.apply(a, None, ww, bias, spec, False, False, 0, False, lazy)
         y.backward(gz)
         torch.cuda.synchronize()

@@ -46,7 +46,7 @@ def _run_op(z, gamma, beta, alpha, ga, dtype, p, small, prefill=None):
     zd = to_act(z, dtype).requires_grad_(True)
     gd, bd = gamma.to(DEV).requires_grad_(True), beta.to(DEV).requires_grad_(True)
     ad = torch.tensor([alpha], device=DEV, requires_grad=True)
-    a = Fn.NormActFn.apply(zd, None, gd, bd, None, cfg, True, None, None, False, None, small, 1, None, None, None, False, ad)
+    a = Fn.NormActFn.apply(zd, None, gd, bd, None, ad, None, None, None, cfg, True, Fn.NormOpts(small=small))
     gact = to_act(ga, dtype)
     a.backward(gact, retain_graph=prefill is not None)
     out = dict(a=from_act(a.detach(), c), dz=from_act(zd.grad, c), dgamma=gd.grad.cpu().clone(), dbeta=bd.grad.cpu().clone(),

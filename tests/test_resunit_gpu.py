@@ -96,7 +96,7 @@ def _run_tail(name, dtype, prefill=None):
             conv.weight.copy_(t["w"]), conv.bias.copy_(t["b"])
         wd, wb, spec = conv.weight, conv.bias, conv.spec
         params += [wd, wb]
-    y = Fn.ResTailFn.apply(zd, None, xd, gd, bd, None, wd, wb, spec, cfg, True, None, None, None)
+    y = Fn.ResTailFn.apply(zd, None, xd, gd, bd, None, wd, wb, None, None, None, spec, cfg, True)
     gact = to_act(t["dy"], dtype)
     y.backward(gact, retain_graph=prefill is not None)
     out = dict(y_act=y.detach().clone(), y=from_act(y.detach(), c), dz=from_act(zd.grad, c), dx=from_act(xd.grad, cx),

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import os
 import weakref
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
@@ -696,6 +696,16 @@ def _grad_done(sink, p, grad, jobs=None):
     return None
 
 
+def _bias_colsum_grad(bias, dz, cout):
+    """A convolution's bias gradient, the per-channel sum of ``dz``: written (second use: added) into the parameter's gradient
+    storage, or -- no sink -- a fresh vector of the ``cout`` real channels.  Returns what autograd gets."""
+    if sink_of(bias) is None:
+        return ops.colsum(dz)[:cout].contiguous()
+    sink, db, acc, _ = _grad_target(bias)
+    ops.colsum_into(dz, db, accumulate=acc)
+    return _grad_done(sink, bias, db)
+
+
 class ConvFn(Function):
     """z = conv(x0 | x1) + bias  (optionally with fused per-tile channel statistics)."""
     wgrad_first = False         # backward: weight gradient before the data gradient (bench.py --wgrad-first).  Measured: 10.018 against
@@ -862,17 +872,15 @@ class ConvFn(Function):
             bsink = sink_of(bias)
             if ctx.zero_bias_grad:                  # (with a sink: its slice of the bucket is zero and nobody ever writes it)
                 db = _grad_done(bsink, bias, _cached_zeros(spec.cout, dev) if bsink is None else None)
-            elif bsink is None and carried is None:
-                db = ops.colsum(dz)[: spec.cout].contiguous()
-            else:
+            elif carried is not None or (side and bsink is not None):
                 bsink, dbt, bacc, _ = _grad_target(bias)
                 if carried is not None:
                     ops.colsum_from_parts(carried[0], carried[1], dbt, accumulate=bacc)
-                elif side:
-                    SideStream.run(lambda: ops.colsum_into(dz, dbt, accumulate=bacc), dz)
                 else:
-                    ops.colsum_into(dz, dbt, accumulate=bacc)
+                    SideStream.run(lambda: ops.colsum_into(dz, dbt, accumulate=bacc), dz)
                 db = _grad_done(bsink, bias, dbt)
+            else:
+                db = _bias_colsum_grad(bias, dz, spec.cout)
         if run_dgrad:
             dx0, dx1 = dgrad()
         return dx0, dx1, dw, db, None, None, None, None, None, None
@@ -979,12 +987,7 @@ class SplitS2dConvFn(Function):
                            dw_offset=cx * k ** 3, defer=defer)
             dw = _grad_done(wsink, weight, dwt, defer)
         if ctx.bias_param is not None and ctx.needs_input_grad[3]:
-            if sink_of(ctx.bias_param) is None:
-                db = ops.colsum(dz)[: spec.cout].contiguous()
-            else:
-                bsink, dbt, acc, _ = _grad_target(ctx.bias_param)
-                ops.colsum_into(dz, dbt, accumulate=acc)
-                db = _grad_done(bsink, ctx.bias_param, dbt)
+            db = _bias_colsum_grad(ctx.bias_param, dz, spec.cout)
         return None, dsy, dw, db, None, None, None, None
 
 
@@ -1151,102 +1154,145 @@ def begin_step(device):
     Fp8Scales.advance(device)
 
 
-NORMACT_INPUTS = 18         # NormActFn.forward's arguments after ctx: its backward returns one entry for each
+class NormOpts(NamedTuple):
+    """What a NormActFn node is asked for beyond norm + dropout + activation; a request it cannot serve (see forward) is dropped.
+    bn_groups: BatchNorm statistics per consecutive sample group (two forward calls of the discriminator stacked along the
+    batch: each group is normalised with its own batch statistics, the running statistics receive the groups' momentum updates
+    in order -- exactly what two separate calls do).  emit8 / emit8_bwd: the fp8 convolution after this node / the fp8 data
+    gradient of the convolution before it reads an e4m3 copy of a / dz: the kernel that writes the bf16 tensor writes the copy too."""
+    s2d_out: bool = False       # return S(a), the space-to-depth tensor the next k4 s2 p1 block reads, instead of the plain a
+    small: bool = False         # small tensor (ops.norm_is_small): statistics, norm, dropout and activation in ONE launch
+    bn_groups: int = 1
+    emit8: Optional["Fp8Scales.Slot"] = None
+    emit8_bwd: Optional["Fp8Scales.Slot"] = None
+    final: Optional[tuple] = None   # (weight, bias, skip_a) of the 1x1x1 convolution that is this node's ONLY consumer
+    pool_after: bool = False    # the activation's only consumer is SkipPoolFn (nn.Down.forward_skip)
+
+
+def _norm_statistics(z, part, conv_bias, cfg: NormCfg, training, running_mean, running_var, batches_tracked, bn_groups=1,
+                     in_launch=False):
+    """Where a norm node's statistics come from -> (groups, mean, rstd, batch_stats, running).  batch_stats: the batch's own
+    (instance norm; BatchNorm in training mode or without running statistics) -- from the partials ``part`` the convolution's
+    launch emitted (taken about ``conv_bias``) or a reduction over z, finalized per group; ``running``: the buffers that launch
+    updates (running_mean, running_var, batches_tracked), or Nones.  in_launch: the caller's kernel computes batch statistics
+    itself (the small-tensor launch): mean / rstd come back None, nothing is launched."""
+    n, d, h, w, c = z.shape
+    if cfg.kind == "none":
+        return 1, None, None, False, (None,) * 3
+    if cfg.kind == "batch" and not training and running_mean is not None:
+        # eval mode: every sample is normalised with the SAME running statistics: one (1, c) mean / rstd row, one group --
+        # whatever bn_groups says (a stacked forward_pair on a model in .eval(): ADVICE r3)
+        mean = _padded(running_mean, c).reshape(1, c)
+        rstd = torch.rsqrt(_padded(running_var, c, 1.0) + cfg.eps).reshape(1, c)
+        return 1, mean, rstd, False, (None,) * 3
+    groups = n if cfg.kind == "instance" else bn_groups
+    assert n % groups == 0
+    count = n * d * h * w // groups
+    if count <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
+    upd = cfg.kind == "batch" and training and running_mean is not None
+    running = (running_mean, running_var, batches_tracked) if upd else (None,) * 3
+    if in_launch:
+        return groups, None, None, True, running
+    if part is not None and part.numel() > 0:
+        assert part.shape[2] == c, "fused statistics need coutp == padded channels"
+        ppg = part.shape[0] // groups
+        shift = conv_bias.detach() if conv_bias is not None else None
+    else:
+        (part, ppg), shift = ops.channel_stats(z, groups), None
+    n_real = running_mean.numel() if upd else (shift.numel() if shift is not None else 0)
+    mean, rstd = ops.norm_finalize(part, ppg, groups, c, count, shift, cfg.eps, running[0], running[1], cfg.momentum, n_real=n_real,
+                                   batches_tracked=running[2])
+    return groups, mean, rstd, True, running
+
+
+def _affine_grad_target(gamma_p, beta_p, both: bool):
+    """Where a norm's affine gradients go -> (sink, keyword arguments for the backward launch).  ``both`` wanted and in one sink:
+    the kernels write (second use: add) them straight into the parameters' .grad storage (gradsink.py); else fresh vectors."""
+    sink = sink_of(gamma_p) if (both and sink_of(beta_p) is sink_of(gamma_p)) else None
+    if sink is None:
+        return None, {}
+    _, dg_t, acc, _ = _grad_target(gamma_p)
+    return sink, dict(affine_into=(dg_t, sink_grad(beta_p)), accumulate=acc)
+
+
+def _affine_grad_done(sink, gamma_p, beta_p, dgamma, dbeta, nch, need_g, need_b):
+    """The backward launch is enqueued: tell the sink, or cut the fresh vectors to the ``nch`` real channels -> what autograd gets"""
+    return (_grad_done(sink, gamma_p, dgamma[:nch].contiguous() if (dgamma is not None and need_g) else None),
+            _grad_done(sink, beta_p, dbeta[:nch].contiguous() if (dbeta is not None and need_b) else None))
 
 
 class NormActFn(Function):
     """a = LeakyReLU(Dropout(Norm(z)))  -- MONAI ADN "NDA" / BatchNorm3d + LeakyReLU; with cfg.act == "prelu" a = PReLU(...) and
-    ``alpha`` (the last input, f32[1]) is its trained slope: read on the device by every launch, its gradient returned."""
+    ``alpha`` (f32[1]) is its trained slope: read on the device by every launch, its gradient returned.  part / conv_bias: the
+    convolution's fused statistics and the bias they were taken about (_norm_statistics); opts: NormOpts."""
 
     @staticmethod
-    def forward(ctx, z, part, gamma, beta, conv_bias, cfg: NormCfg, training, running_mean, running_var,
-                s2d_out: bool = False, batches_tracked=None, small: bool = False, bn_groups: int = 1,
-                emit8=None, emit8_bwd=None, final=None, pool_after: bool = False, alpha=None):
-        """bn_groups > 1: BatchNorm statistics per consecutive sample group (two forward calls of the discriminator stacked
-        along the batch: each group is normalised with its own batch statistics, the running statistics receive the groups'
-        momentum updates in order -- exactly what two separate calls do)."""
-        # emit8 / emit8_bwd (Fp8Scales.Slot or None): the fp8 convolution after this node / the fp8 data gradient of the
-        # convolution before it reads an e4m3 copy of a / dz: the kernel that writes the bf16 tensor writes the copy too
+    def _positional(cfg, training, running_mean, running_var, s2d_out=False, batches_tracked=None, small=False, bn_groups=1,
+                    emit8=None, emit8_bwd=None, final=None, pool_after=False, alpha=None):
+        """what followed conv_bias in the positional form from before NormOpts -> what follows it in forward"""
+        return (alpha, running_mean, running_var, batches_tracked, cfg, training,
+                NormOpts(s2d_out, small, bn_groups, emit8, emit8_bwd, final, pool_after))
+
+    @classmethod
+    def apply(cls, z, part, gamma, beta, conv_bias, *rest):
+        # a NormCfg where forward has alpha (a tensor or None): a caller written for the positional form, which stays served
+        if rest and isinstance(rest[0], NormCfg):
+            rest = cls._positional(*rest)
+        return super().apply(z, part, gamma, beta, conv_bias, *rest)
+
+    @staticmethod
+    def forward(ctx, z, part, gamma, beta, conv_bias, alpha, running_mean, running_var, batches_tracked, cfg: NormCfg, training,
+                opts: NormOpts = NormOpts()):
         z = ops.as_act(z)
         n, d, h, w, c = z.shape
-        rows = n * d * h * w
         if (cfg.act == "prelu") != (alpha is not None) or (alpha is not None and cfg.kind == "none"):
             raise ValueError("NormActFn: a PReLU node takes its slope as `alpha` (and a norm); a LeakyReLU node takes none")
-        # statistics of the batch itself (instance norm; BatchNorm in training mode or without running statistics)?  In eval
-        # mode BatchNorm normalises every sample with the SAME running statistics: one (1, c) mean / rstd row, one group --
-        # whatever bn_groups says (a stacked forward_pair on a model in .eval(): ADVICE r3)
-        use_batch = cfg.kind == "instance" or (cfg.kind == "batch" and (training or running_mean is None))
-        groups = n if cfg.kind == "instance" else (bn_groups if (cfg.kind == "batch" and use_batch) else 1)
-        assert n % groups == 0
-        mean = rstd = None
-        batch_stats = False
-        ctx.emit8_bwd = emit8_bwd if (emit8_bwd is not None and emit8_bwd.primed and not small and not s2d_out) else None
-        if emit8 is not None and not (emit8.primed and not small and not s2d_out and z.dtype == torch.bfloat16 and c == 32):
-            emit8 = None
-        small = small and cfg.kind != "none" and use_batch      # statistics, norm, dropout and activation in ONE launch
-        upd = cfg.kind == "batch" and training and running_mean is not None
-        if cfg.kind != "none" and use_batch and rows // groups <= 1:
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
-        if small:
-            batch_stats = True
-        elif cfg.kind != "none":
-            if use_batch:
-                if part is not None and part.numel() > 0:
-                    assert part.shape[2] == c, "fused statistics need coutp == padded channels"
-                    ppg = part.shape[0] // groups
-                    shift = conv_bias.detach() if conv_bias is not None else None
-                else:
-                    part, ppg = ops.channel_stats(z, groups)
-                    shift = None
-                n_real = running_mean.numel() if upd else (shift.numel() if shift is not None else 0)
-                mean, rstd = ops.norm_finalize(part, ppg, groups, c, rows // groups, shift, cfg.eps,
-                                               running_mean if upd else None, running_var if upd else None,
-                                               cfg.momentum, n_real=n_real,
-                                               batches_tracked=batches_tracked if upd else None)
-                batch_stats = True
-            else:
-                mean = _padded(running_mean, c).reshape(1, c)
-                rstd = torch.rsqrt(_padded(running_var, c, 1.0) + cfg.eps).reshape(1, c)
-        gp = gamma.detach() if gamma is not None else None      # kernels guard the (possibly shorter) length
-        bp = beta.detach() if beta is not None else None
+        groups, mean, rstd, batch_stats, running = _norm_statistics(z, part, conv_bias, cfg, training, running_mean, running_var,
+                                                                    batches_tracked, opts.bn_groups, in_launch=opts.small)
+        # which launch: the one-launch small-tensor kernel (it needs batch statistics to compute), else the streaming kernel in ONE
+        # of its forms -- S(a) out, + e4m3 copy, + final convolution, + max-pool, plain -- the first one asked for that it can serve.
+        # The e4m3 copies and the final convolution exist for 32 bf16 channels in the plain layout only; a node that was ASKED for
+        # the small kernel writes no e4m3 copy even where it falls back to the streaming one.
+        small = opts.small and batch_stats
+        bf16_32 = z.dtype == torch.bfloat16 and c == 32
+        can8 = bf16_32 and not opts.small and not opts.s2d_out
+        emit8 = opts.emit8 if (can8 and opts.emit8 is not None and opts.emit8.primed) else None
+        ctx.emit8_bwd = opts.emit8_bwd if (can8 and opts.emit8_bwd is not None and opts.emit8_bwd.primed) else None
+        # (the kernels guard gamma / beta's possibly shorter length; alpha is a pointer for them, never read on the host)
+        gp, bp, ap = (t.detach() if t is not None else None for t in (gamma, beta, alpha))
         p = cfg.p if training else 0.0
-        seed = DropoutState.next_salt() if p > 0.0 else 0
-        seed_t = DropoutState.base(z.device) if p > 0.0 else None
-        ap = alpha.detach() if alpha is not None else None       # (a pointer for the kernels: never read on the host)
+        seed, seed_t = (DropoutState.next_salt(), DropoutState.base(z.device)) if p > 0.0 else (0, None)
+        out = _new_s2d(ops.s2d_shape(n, d, h, w, c), z.dtype, z.device) if opts.s2d_out else None
+
+        def launch(**form):
+            return ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t, alpha=ap, **form)
+
         if small:
             # small tensor (low U-Net levels, last PatchGAN blocks)
-            out = _new_s2d(ops.s2d_shape(n, d, h, w, c), z.dtype, z.device) if s2d_out else None
-            a, mean, rstd = ops.normact_small_fwd(z, groups, gp, bp, cfg.eps, cfg.slope, p, seed, seed_t,
-                                                  running_mean if upd else None, running_var if upd else None, cfg.momentum,
-                                                  batches_tracked if upd else None, out=out, s2d=s2d_out, alpha=ap)
-        elif s2d_out:
-            out = _new_s2d(ops.s2d_shape(n, d, h, w, c), z.dtype, z.device)
-            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, out=out, s2d=True, seed_t=seed_t, alpha=ap)
+            a, mean, rstd = ops.normact_small_fwd(z, groups, gp, bp, cfg.eps, cfg.slope, p, seed, seed_t, running[0], running[1],
+                                                  cfg.momentum, running[2], out=out, s2d=opts.s2d_out, alpha=ap)
+        elif opts.s2d_out:
+            a = launch(out=out, s2d=True)
         elif emit8 is not None:
             a8 = torch.empty(z.shape, dtype=torch.uint8, device=z.device)
-            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t, q8=(a8, emit8.use, emit8.next), alpha=ap)
+            a = launch(q8=(a8, emit8.use, emit8.next))
             emit8.touched = True
             Fp8Side.put(a, a8)
-        elif final is not None and z.dtype == torch.bfloat16 and c == 32:
-            # final = (weight, bias, skip_a) of the 1x1x1 convolution that is this node's ONLY consumer (BasicUNet.final_conv):
-            # computed in the same pass; without autograd (skip_a) the activation itself is not even written
-            fw, fb, skip_a = final               # (skip_a is the CALLER's `not torch.is_grad_enabled()`: in here grad mode is always off)
+        elif opts.final is not None and bf16_32:
+            # the 1x1x1 convolution computed in the same pass; without autograd (skip_a) the activation itself is not even written
+            fw, fb, skip_a = opts.final          # (skip_a comes from the caller: in here grad mode is always off)
             y = ops.new_act(n, d, h, w, round_up(fw.shape[0], 16), z.dtype, z.device)
-            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t,
-                                final=(fw.detach(), fb.detach() if fb is not None else None, y), skip_a=skip_a, alpha=ap)
+            a = launch(final=(fw.detach(), fb.detach() if fb is not None else None, y), skip_a=skip_a)
             FusedFinal.put(a, y, fw, fw._version)
-        elif (pool_after and PoolSide.enabled and not s2d_out and emit8 is None and d % 2 == 0 and h % 2 == 0 and w % 2 == 0
-              and (rows // groups) % (d * h * w) == 0):
-            # the activation's only consumer is SkipPoolFn (nn.Down.forward_skip): its MaxPool3d(2) in this launch (PoolSide)
-            a, py, pidx = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t, pool=True, alpha=ap)
+        elif opts.pool_after and PoolSide.enabled and d % 2 == 0 and h % 2 == 0 and w % 2 == 0:
+            # SkipPoolFn's MaxPool3d(2) in this launch (PoolSide); a statistics group is whole samples, so no window straddles two
+            a, py, pidx = launch(pool=True)
             PoolSide.put(a, py, pidx)
         else:
-            a = ops.normact_fwd(z, groups, mean, rstd, gp, bp, cfg.slope, p, seed, seed_t=seed_t, alpha=ap)
-        ctx.small = small
-        ctx.s2d_out = s2d_out
-        ctx.seed_t = seed_t
-        ctx.affine_params = (gamma, beta)
-        ctx.alpha_param = alpha
+            a = launch()
+        ctx.small, ctx.s2d_out, ctx.seed_t = small, opts.s2d_out, seed_t
+        ctx.affine_params, ctx.alpha_param = (gamma, beta), alpha
         ctx.save_for_backward(z, mean, rstd, gp, bp, ap)
         ctx.meta = (groups, cfg.slope, p, seed, batch_stats, gamma.numel() if gamma is not None else 0)
         return a
@@ -1269,80 +1315,70 @@ class NormActFn(Function):
                 da = ops.maxpool2_bwd(lp[0], lp[1], lp[3], lp[4])     # these kernels read a materialised gradient
             else:
                 pool, da = (lp[2], lp[3]), lp[4]
-        need_g, need_b = ctx.needs_input_grad[2:4]
+        _, _, need_g, need_b, _, need_alpha = ctx.needs_input_grad[:6]
         want_affine = need_g or need_b
         gamma_p, beta_p = ctx.affine_params
-        kw = dict(s2d=ctx.s2d_out, seed_t=ctx.seed_t, alpha=ap)
-        sink = sink_of(gamma_p) if (need_g and need_b and mean is not None and sink_of(beta_p) is sink_of(gamma_p)) else None
-        if sink is not None:
-            # both affine gradients straight into the parameters' .grad storage (gradsink.py)
-            _, dg_t, acc, _ = _grad_target(gamma_p)
-            kw.update(affine_into=(dg_t, sink_grad(beta_p)), accumulate=acc)
+        sink, kw = _affine_grad_target(gamma_p, beta_p, need_g and need_b and mean is not None)
         # PReLU: the slope's gradient comes out of the same launches, written (or accumulated) where the parameter's gradient lives;
         # the launches share one `accumulate` with the affine gradients -- where the two differ it goes through a scalar of its own
         alpha_p, asink, da_t, da_tmp = ctx.alpha_param, None, None, None
-        if alpha_p is not None and ctx.needs_input_grad[NORMACT_INPUTS - 1]:
+        if alpha_p is not None and need_alpha:
             asink, da_t, a_acc, _ = _grad_target(alpha_p)
             if a_acc != bool(kw.get("accumulate", False)):
                 da_tmp = torch.zeros_like(da_t)
             kw.update(dalpha=da_t if da_tmp is None else da_tmp)
+        kw.update(s2d=ctx.s2d_out, seed_t=ctx.seed_t, alpha=ap)
         if ctx.small:
             dz, dgamma, dbeta = ops.normact_small_bwd(z, da, groups, mean, rstd, gp, bp, slope, p, seed, batch_stats,
                                                       want_affine=want_affine, **kw)
         else:
-            slot8 = ctx.emit8_bwd if (z.dtype == torch.bfloat16 and z.shape[4] == 32) else None
+            slot8 = ctx.emit8_bwd
             q8 = (torch.empty(z.shape, dtype=torch.uint8, device=z.device), slot8.use, slot8.next) if slot8 is not None else None
             dz, dgamma, dbeta = ops.normact_bwd(z, da, groups, mean, rstd, gp, bp, slope, p, seed, batch_stats,
                                                 want_affine and mean is not None, q8=q8, implicit=lazy, pool=pool, **kw)
             if q8 is not None:
                 slot8.touched = True
                 Fp8Side.put(dz, q8[0])
-        dg = _grad_done(sink, gamma_p, dgamma[:nch].contiguous() if (dgamma is not None and need_g) else None)
-        dbt = _grad_done(sink, beta_p, dbeta[:nch].contiguous() if (dbeta is not None and need_b) else None)
+        dg, dbt = _affine_grad_done(sink, gamma_p, beta_p, dgamma, dbeta, nch, need_g, need_b)
         dal = None
         if da_t is not None:
             if da_tmp is not None:
                 da_t.add_(da_tmp) if a_acc else da_t.copy_(da_tmp)
             dal = _grad_done(asink, alpha_p, da_t)
-        return (dz, None, dg, dbt) + (None,) * (NORMACT_INPUTS - 5) + (dal,)
+        # z, part, gamma, beta, conv_bias, alpha; then running_mean, running_var, batches_tracked, cfg, training, opts
+        return dz, None, dg, dbt, None, dal, None, None, None, None, None, None
 
 
 class ResTailFn(Function):
     """y = ReLU(Norm(z)) + residual(x): the tail of nn.ResidualUnit (MONAI ResidualUnit, ADN "NDA", no activation after the sum) as
     ONE launch (ops.restail_fwd) instead of a norm + act launch, a 1x1x1 convolution and an add.  z: the last convolution's
     output, part: its fused statistics, x: the block's input; residual(x) = x when ``res_weight`` is None, else the 1x1x1
-    convolution (res_weight, res_bias), ``res_spec`` its ConvSpec.  cfg: NormCfg with slope 0, no dropout, batch or instance
-    statistics from the convolution's partials as in NormActFn (eval-mode BatchNorm: the running statistics as one (1, c) row).
+    convolution (res_weight, res_bias), ``res_spec`` its ConvSpec.  cfg: NormCfg with slope 0, no dropout; statistics as in
+    NormActFn (_norm_statistics, one BatchNorm group).
     Backward: the existing launches -- ops.normact_bwd on z with da = dy (it recomputes the ReLU mask from z), the streaming
     1x1x1 weight gradient and a column sum for the residual convolution, and for x (when it needs one) dy itself or the 1x1x1
     data gradient."""
 
     @staticmethod
-    def forward(ctx, z, part, x, gamma, beta, conv_bias, res_weight, res_bias, res_spec: Optional[ConvSpec], cfg: NormCfg,
-                training, running_mean, running_var, batches_tracked=None):
+    def _positional(res_spec, cfg, training, running_mean, running_var, batches_tracked=None):
+        """what followed res_bias in the earlier positional form -> what follows it in forward"""
+        return running_mean, running_var, batches_tracked, res_spec, cfg, training
+
+    @classmethod
+    def apply(cls, *args):
+        # a NormCfg where forward has running_var (a tensor or None): a caller written for the earlier order, which stays served
+        if len(args) > 9 and isinstance(args[9], NormCfg):
+            args = args[:8] + cls._positional(*args[8:])
+        return super().apply(*args)
+
+    @staticmethod
+    def forward(ctx, z, part, x, gamma, beta, conv_bias, res_weight, res_bias, running_mean, running_var, batches_tracked,
+                res_spec: Optional[ConvSpec], cfg: NormCfg, training):
         z, x = ops.as_act(z), ops.as_act(x)
-        n, d, h, w, c = z.shape
-        rows = n * d * h * w
         if cfg.kind == "none" or cfg.act != "leakyrelu" or cfg.slope != 0.0 or cfg.p != 0.0:
             raise ValueError("ResTailFn: a norm followed by ReLU, without dropout")
-        use_batch = cfg.kind == "instance" or training or running_mean is None
-        groups = n if cfg.kind == "instance" else 1
-        if use_batch:
-            if rows // groups <= 1:
-                raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
-            upd = cfg.kind == "batch" and training and running_mean is not None
-            if part is not None and part.numel() > 0:
-                assert part.shape[2] == c, "fused statistics need coutp == padded channels"
-                ppg, shift = part.shape[0] // groups, (conv_bias.detach() if conv_bias is not None else None)
-            else:
-                (part, ppg), shift = ops.channel_stats(z, groups), None
-            n_real = running_mean.numel() if upd else (shift.numel() if shift is not None else 0)
-            mean, rstd = ops.norm_finalize(part, ppg, groups, c, rows // groups, shift, cfg.eps, running_mean if upd else None,
-                                           running_var if upd else None, cfg.momentum, n_real=n_real,
-                                           batches_tracked=batches_tracked if upd else None)
-        else:
-            mean = _padded(running_mean, c).reshape(1, c)
-            rstd = torch.rsqrt(_padded(running_var, c, 1.0) + cfg.eps).reshape(1, c)
+        groups, mean, rstd, batch_stats, _ = _norm_statistics(z, part, conv_bias, cfg, training, running_mean, running_var,
+                                                              batches_tracked)
         gp, bp = gamma.detach(), beta.detach()
         rw = res_weight.detach() if res_weight is not None else None
         rb = res_bias.detach() if res_bias is not None else None
@@ -1351,7 +1387,7 @@ class ResTailFn(Function):
         ctx.save_for_backward(z, x, mean, rstd, gp, bp)
         ctx.params = (gamma, beta, res_weight, res_bias)
         ctx.res_spec = res_spec
-        ctx.meta = (groups, use_batch, cfg.channels)
+        ctx.meta = (groups, batch_stats, cfg.channels)
         return y
 
     @staticmethod
@@ -1367,14 +1403,9 @@ class ResTailFn(Function):
         dz = dg = dbt = dx = drw = drb = None
         if need_z or need_g or need_b:
             # norm + ReLU: exactly NormActFn's launches with slope 0 and no dropout
-            kw = {}
-            sink = sink_of(gamma_p) if (need_g and need_b and sink_of(beta_p) is sink_of(gamma_p)) else None
-            if sink is not None:
-                _, dg_t, acc, _ = _grad_target(gamma_p)
-                kw.update(affine_into=(dg_t, sink_grad(beta_p)), accumulate=acc)
+            sink, kw = _affine_grad_target(gamma_p, beta_p, need_g and need_b)
             dz, dgamma, dbeta = ops.normact_bwd(z, dy, groups, mean, rstd, gp, bp, 0.0, 0.0, 0, batch_stats, need_g or need_b, **kw)
-            dg = _grad_done(sink, gamma_p, dgamma[:nch].contiguous() if (dgamma is not None and need_g) else None)
-            dbt = _grad_done(sink, beta_p, dbeta[:nch].contiguous() if (dbeta is not None and need_b) else None)
+            dg, dbt = _affine_grad_done(sink, gamma_p, beta_p, dgamma, dbeta, nch, need_g, need_b)
         if rw_p is None:
             dx = dy if need_x else None
         else:
@@ -1388,12 +1419,8 @@ class ResTailFn(Function):
                                (0, 0, 0), (1, 1, 1), accumulate=acc, defer=defer)
                 drw = _grad_done(wsink, rw_p, dwt, defer)
             if rb_p is not None and need_rb:
-                if sink_of(rb_p) is None:
-                    drb = ops.colsum(dy)[: spec.cout].contiguous()
-                else:
-                    bsink, dbt_, bacc, _ = _grad_target(rb_p)
-                    ops.colsum_into(dy, dbt_, accumulate=bacc)
-                    drb = _grad_done(bsink, rb_p, dbt_)
+                drb = _bias_colsum_grad(rb_p, dy, spec.cout)
+        # z, part, x, gamma, beta, conv_bias, res_weight, res_bias; then the running buffers, res_spec, cfg, training
         return dz, None, dx, dg, dbt, None, drw, drb, None, None, None, None, None, None
 
 

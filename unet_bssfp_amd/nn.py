@@ -211,10 +211,11 @@ class DownSampleConv(_Mi355Module):
             return z
         if self.batchnorm:
             # num_batches_tracked is advanced by the statistics kernel (no launch of its own)
-            return Fn.NormActFn.apply(z, part if (fuse and not small) else None, self.bn.weight, self.bn.bias, self.conv.bias,
-                                      self.cfg, self.training, self.bn.running_mean, self.bn.running_var, s2d_out,
-                                      self.bn.num_batches_tracked if self.training else None, small, bn_groups)
-        return Fn.NormActFn.apply(z, None, None, None, None, self.cfg, self.training, None, None, s2d_out)
+            bn, nbt = self.bn, self.bn.num_batches_tracked if self.training else None
+            return Fn.NormActFn.apply(z, part if (fuse and not small) else None, bn.weight, bn.bias, self.conv.bias, None,
+                                      bn.running_mean, bn.running_var, nbt, self.cfg, self.training,
+                                      Fn.NormOpts(s2d_out=s2d_out, small=small, bn_groups=bn_groups))
+        return Fn.NormActFn.apply(z, None, None, None, None, None, None, None, None, self.cfg, self.training, Fn.NormOpts(s2d_out=s2d_out))
 
     def forward(self, x):
         return self._from_act(self.forward_act(self._to_act(x)), self.conv.out_channels)
@@ -308,10 +309,10 @@ class ResidualUnit(_Mi355Module):
             if fused:
                 proj = isinstance(self.residual, Conv3d)
                 return Fn.ResTailFn.apply(z, part, x, bn.weight, bn.bias, unit.conv.bias, self.residual.weight if proj else None,
-                                          self.residual.bias if proj else None, self.residual.spec if proj else None, self.cfg,
-                                          self.training, *running)
-            a = Fn.NormActFn.apply(z, part if (stats and not small) else None, bn.weight, bn.bias, unit.conv.bias, self.cfg,
-                                   self.training, running[0], running[1], False, running[2], small)
+                                          self.residual.bias if proj else None, *running, self.residual.spec if proj else None,
+                                          self.cfg, self.training)
+            a = Fn.NormActFn.apply(z, part if (stats and not small) else None, bn.weight, bn.bias, unit.conv.bias, None, *running,
+                                   self.cfg, self.training, Fn.NormOpts(small=small))
         res = self.residual.forward_act(x)[0] if isinstance(self.residual, Conv3d) else x
         return a + res
 
@@ -526,9 +527,9 @@ class Convolution(_Mi355Module):
                 and final.in_channels <= cp and Fn.LazyDx.enabled):
             # `final` is the 1x1x1 convolution that is this block's only consumer: evaluated by the norm + act launch itself
             fin = (final.weight, final.bias, not torch.is_grad_enabled())
-        return Fn.NormActFn.apply(z, part if not small else None, self.adn.N.weight, self.adn.N.bias, shift, self.cfg,
-                                  self.training, None, None, False, None, small, 1, emit8, emit8_bwd, fin, pool_after,
-                                  self.adn.A.weight if self.cfg.act == "prelu" else None)
+        return Fn.NormActFn.apply(z, part if not small else None, self.adn.N.weight, self.adn.N.bias, shift,
+                                  self.adn.A.weight if self.cfg.act == "prelu" else None, None, None, None, self.cfg, self.training,
+                                  Fn.NormOpts(small=small, emit8=emit8, emit8_bwd=emit8_bwd, final=fin, pool_after=pool_after))
 
 
 class TwoConv(_Mi355Module):

@@ -4,6 +4,7 @@ channel slice of a wider buffer), dtype float32 (parity mode) or bfloat16 (throu
 PyTorch is used for device memory and streams only."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import NamedTuple, Optional, Sequence, Tuple
 
@@ -611,11 +612,48 @@ def _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_
 NORM_PROBE = None
 
 
-def _norm_probe(kind, z, gamma):
-    if NORM_PROBE is None:
-        return None
-    n, dd, h, w, c = z.shape
-    return NORM_PROBE(kind, gamma.numel() if gamma is not None else c, n * dd * h * w, z.element_size())
+@contextlib.contextmanager
+def _norm_probed(kind, z, gamma):
+    """the launches of one norm + act wrapper, bracketed by NORM_PROBE when one is set"""
+    after = None
+    if NORM_PROBE is not None:
+        n, dd, h, w, c = z.shape
+        after = NORM_PROBE(kind, gamma.numel() if gamma is not None else c, n * dd * h * w, z.element_size())
+    yield
+    if after is not None:
+        after()
+
+
+def _set_extents(d, z, flag=None):
+    """z's plain extents, for the launches that address voxels: the S layout (flag "s2d_a": the forward writes S(a); "s2d_da": the
+    backward reads a gradient in S layout) and MaxPool3d(2) inside the launch -> the pooled tensor's shape"""
+    n, d.sd, d.sh, d.sw, c = z.shape
+    if flag:
+        setattr(d, flag, 1)
+    return n, d.sd // 2, d.sh // 2, d.sw // 2, c
+
+
+def _check_dalpha(who, dalpha, alpha, affine_into, accumulate, norm=None):
+    """a slope gradient (f32[1]) needs the slope on the device and (norm: False / True where the caller can be without one) a
+    norm; it shares `accumulate` with the affine gradients"""
+    require_cuda(dalpha)
+    if alpha is None or norm is False:
+        raise ValueError(f"{who}: a slope gradient needs the slope on the device (alpha)" + ("" if norm is None else " and a norm"))
+    if accumulate and affine_into is None:
+        raise ValueError(f"{who}: accumulate goes with affine_into (fresh affine gradients have nothing to add to)")
+    assert dalpha.dtype == torch.float32 and dalpha.numel() == 1
+
+
+def _affine_targets(z, affine_into, fresh):
+    """-> (dgamma, dbeta, caller-owned?): the caller's f32 vectors of the real channel count, else padded ones made by ``fresh``
+    (torch.empty for the streaming kernels, which write every entry; torch.zeros for the small-tensor kernel, which does not)"""
+    c = z.shape[4]
+    if affine_into is None:
+        return fresh((c,), dtype=torch.float32, device=z.device), fresh((c,), dtype=torch.float32, device=z.device), False
+    g_into, b_into = affine_into
+    require_cuda(g_into, b_into)
+    assert g_into.dtype == b_into.dtype == torch.float32 and g_into.numel() == b_into.numel() <= c
+    return g_into, b_into, True
 
 
 def _set_q8(d, q8):
@@ -641,37 +679,30 @@ def normact_fwd(z, groups, mean, rstd, gamma, beta, slope, drop_p=0.0, seed=0, o
         out = torch.empty(z.shape, dtype=z.dtype, device=z.device)
     d = _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t, alpha)
     d.a, d.lda = out.data_ptr(), act_ld(out)
-    keep_final = None
     if final is not None:
         fw, fb, fy = final
         require_cuda(fw, fb, fy)
         assert not s2d and z.dtype == fy.dtype == torch.bfloat16 and fw.dtype == torch.float32 and fw.is_contiguous()
-        fw2 = fw.detach().reshape(fw.shape[0], -1)
+        fw2 = fw.detach().reshape(fw.shape[0], -1)           # (a view: fw is contiguous, so the caller's tensor backs the pointer)
         assert fw2.shape[0] <= 8 and fw2.shape[1] <= z.shape[4] and tuple(fy.shape[:4]) == tuple(z.shape[:4])
         assert fb is None or (fb.dtype == torch.float32 and fb.numel() == fw2.shape[0])
         d.gw, d.gw_ld, d.gk = fw2.data_ptr(), fw2.shape[1], fw2.shape[0]
-        d.fy, d.ldfy, d.fcp, d.fbias = fy.data_ptr(), act_ld(fy), fy.shape[4], _ptr(fb.detach() if fb is not None else None)
+        d.fy, d.ldfy, d.fcp, d.fbias = fy.data_ptr(), act_ld(fy), fy.shape[4], _ptr(fb)
         d.skip_a = 1 if skip_a else 0
-        keep_final = (fw2, fb, fy)
     else:
         assert not skip_a
     if q8 is not None:
         _set_q8(d, q8)
     if s2d:
-        d.s2d_a = 1
-        d.sd, d.sh, d.sw = z.shape[1:4]
+        _set_extents(d, z, "s2d_a")
     py = pidx = None
     if pool:
-        n, dd, h, w, c = z.shape
-        assert not s2d and q8 is None and final is None and dd % 2 == 0 and h % 2 == 0 and w % 2 == 0
-        py = torch.empty((n, dd // 2, h // 2, w // 2, c), dtype=z.dtype, device=z.device)
+        assert not s2d and q8 is None and final is None and not any(e % 2 for e in z.shape[1:4])
+        py = torch.empty(_set_extents(d, z), dtype=z.dtype, device=z.device)
         pidx = torch.empty(py.shape, dtype=torch.uint8, device=z.device)
         d.pool_y, d.ldpy, d.pool_widx = py.data_ptr(), act_ld(py), pidx.data_ptr()
-        d.sd, d.sh, d.sw = dd, h, w
-    after = _norm_probe("fwd", z, gamma)
-    _lib.check(_lib.load().mi355_normact_fwd(C.byref(d), _stream()), "normact_fwd")
-    if after is not None:
-        after()
+    with _norm_probed("fwd", z, gamma):
+        _lib.check(_lib.load().mi355_normact_fwd(C.byref(d), _stream()), "normact_fwd")
     return (out, py, pidx) if pool else out
 
 
@@ -694,27 +725,22 @@ def normact_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, seed, bat
     rows = n * dd * h * w
     d = _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t, alpha)
     if dalpha is not None:
-        require_cuda(dalpha)
-        if alpha is None or mean is None:
-            raise ValueError("normact_bwd: a slope gradient needs the slope on the device (alpha) and a norm")
-        assert dalpha.dtype == torch.float32 and dalpha.numel() == 1
-    keep_implicit = None
+        _check_dalpha("normact_bwd", dalpha, alpha, affine_into, accumulate, norm=mean is not None)
     if implicit is not None:
         gz, gw = implicit
         require_cuda(gz, gw)
         assert da is None and not s2d and z.dtype == torch.bfloat16 and gz.dtype == torch.bfloat16
         assert tuple(gz.shape[:4]) == tuple(z.shape[:4]) and gw.dtype == torch.float32 and gw.is_contiguous()
-        gw2 = gw.detach().reshape(gw.shape[0], -1)
+        gw2 = gw.detach().reshape(gw.shape[0], -1)           # (a view: gw is contiguous, so the caller's tensor backs the pointer)
         assert gw2.shape[0] <= 8 and gw2.shape[0] <= gz.shape[4] and gw2.shape[1] <= c
         d.gz, d.ldgz, d.gw, d.gw_ld, d.gk = gz.data_ptr(), act_ld(gz), gw2.data_ptr(), gw2.shape[1], gw2.shape[0]
-        keep_implicit = (gz, gw2)
     elif pool is not None:
         pidx, pdy = pool
         require_cuda(pidx, pdy)
         assert not s2d and pidx.dtype == torch.uint8 and pidx.is_contiguous() and pdy.dtype == z.dtype
-        assert tuple(pidx.shape) == (n, dd // 2, h // 2, w // 2, c) == tuple(pdy.shape) and dd % 2 == 0 and h % 2 == 0 and w % 2 == 0
+        pooled = _set_extents(d, z)
+        assert tuple(pidx.shape) == pooled == tuple(pdy.shape) and not any(e % 2 for e in z.shape[1:4])
         d.pool_idx, d.pool_dy, d.ldpdy = pidx.data_ptr(), pdy.data_ptr(), act_ld(pdy)
-        d.sd, d.sh, d.sw = dd, h, w
         if da is not None:
             assert tuple(da.shape) == tuple(z.shape) and da.dtype == z.dtype
             d.da, d.ldda = da.data_ptr(), act_ld(da)
@@ -724,58 +750,44 @@ def normact_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, seed, bat
     d.dz, d.lddz = dz.data_ptr(), act_ld(dz)
     d.batch_stats = 1 if batch_stats else 0
     if s2d:
-        d.s2d_da = 1
-        d.sd, d.sh, d.sw = z.shape[1:4]
+        _set_extents(d, z, "s2d_da")
     if q8 is not None:
         _set_q8(d, q8)                      # e4m3 copy of dz for the fp8 data-gradient convolution
     dgamma = dbeta = None
-    keep = []
-    after = _norm_probe("bwd", z, gamma)
-    if mean is not None and (batch_stats or want_affine_grads or dalpha is not None):
-        bpg = lib.mi355_channel_stats_blocks(rows // groups)
-        # one buffer of rows of c floats: the partials [groups * bpg][2][c]; behind them, for a slope gradient, its partials
-        # [groups * bpg][c] and the per-channel totals (c doubles = 2 rows; the offset is a multiple of 16 bytes)
-        nparts = groups * bpg
-        nrows = 2 * nparts if dalpha is None else 3 * nparts + 2
-        buf = torch.empty((nrows, c), dtype=torch.float32, device=z.device)
-        part = buf[:2 * nparts]
-        d.part, d.blocks_per_group = part.data_ptr(), bpg
-        if dalpha is not None:
-            apart, alpha_ch = buf[2 * nparts: 3 * nparts], buf[3 * nparts:]
-            d.dalpha, d.dalpha_part = dalpha.data_ptr(), apart.data_ptr()
-        _lib.check(lib.mi355_normact_bwd_reduce(C.byref(d), _stream()), "normact_bwd_reduce")
-        sums = torch.empty((groups, 2, c), dtype=torch.float32, device=z.device)
-        if affine_into is not None:
-            g_into, b_into = affine_into
-            require_cuda(g_into, b_into)
-            assert g_into.dtype == b_into.dtype == torch.float32 and g_into.numel() == b_into.numel() <= c
-        else:
-            dgamma = torch.empty((c,), dtype=torch.float32, device=z.device)
-            dbeta = torch.empty((c,), dtype=torch.float32, device=z.device)
-        if dalpha is not None:
-            if affine_into is None and accumulate:
-                raise ValueError("normact_bwd: accumulate goes with affine_into (fresh affine gradients have nothing to add to)")
-            # (n_affine: the real channels -- padded channels add nothing to the slope gradient, and their affine gradients
-            #  are not written)
-            g_t, b_t = (g_into, b_into) if affine_into is not None else (dgamma, dbeta)
-            n_aff = g_into.numel() if affine_into is not None else (d.n_affine or c)
-            _lib.check(lib.mi355_normact_bwd_finalize_prelu(part.data_ptr(), apart.data_ptr(), bpg, groups, c, sums.data_ptr(),
-                                                            g_t.data_ptr(), b_t.data_ptr(), n_aff, 1 if accumulate else 0,
-                                                            alpha_ch.data_ptr(), dalpha.data_ptr(), _stream()),
-                       "normact_bwd_finalize_prelu")
-        elif affine_into is not None:
-            _lib.check(lib.mi355_normact_bwd_finalize_into(part.data_ptr(), bpg, groups, c, sums.data_ptr(),
-                                                           g_into.data_ptr(), b_into.data_ptr(), g_into.numel(),
-                                                           1 if accumulate else 0, _stream()), "normact_bwd_finalize")
-        else:
-            _lib.check(lib.mi355_normact_bwd_finalize(part.data_ptr(), bpg, groups, c, sums.data_ptr(),
-                                                      dgamma.data_ptr(), dbeta.data_ptr(), _stream()),
-                       "normact_bwd_finalize")
-        d.sums = sums.data_ptr()
-        keep += [part, sums]
-    _lib.check(lib.mi355_normact_bwd_apply(C.byref(d), _stream()), "normact_bwd_apply")
-    if after is not None:
-        after()
+    with _norm_probed("bwd", z, gamma):
+        if mean is not None and (batch_stats or want_affine_grads or dalpha is not None):
+            bpg = lib.mi355_channel_stats_blocks(rows // groups)
+            # one buffer of rows of c floats: the partials [groups * bpg][2][c]; behind them, for a slope gradient, its partials
+            # [groups * bpg][c] and the per-channel totals (c doubles = 2 rows; the offset is a multiple of 16 bytes)
+            nparts = groups * bpg
+            nrows = 2 * nparts if dalpha is None else 3 * nparts + 2
+            buf = torch.empty((nrows, c), dtype=torch.float32, device=z.device)
+            part = buf[:2 * nparts]
+            d.part, d.blocks_per_group = part.data_ptr(), bpg
+            if dalpha is not None:
+                apart, alpha_ch = buf[2 * nparts: 3 * nparts], buf[3 * nparts:]
+                d.dalpha, d.dalpha_part = dalpha.data_ptr(), apart.data_ptr()
+            _lib.check(lib.mi355_normact_bwd_reduce(C.byref(d), _stream()), "normact_bwd_reduce")
+            sums = torch.empty((groups, 2, c), dtype=torch.float32, device=z.device)
+            g_t, b_t, owned = _affine_targets(z, affine_into, torch.empty)
+            if dalpha is not None:
+                # (n_affine: the real channels -- padded channels add nothing to the slope gradient, and their affine gradients
+                #  are not written)
+                n_aff = g_t.numel() if owned else (d.n_affine or c)
+                _lib.check(lib.mi355_normact_bwd_finalize_prelu(part.data_ptr(), apart.data_ptr(), bpg, groups, c, sums.data_ptr(),
+                                                                g_t.data_ptr(), b_t.data_ptr(), n_aff, int(accumulate),
+                                                                alpha_ch.data_ptr(), dalpha.data_ptr(), _stream()),
+                           "normact_bwd_finalize_prelu")
+            elif owned:
+                _lib.check(lib.mi355_normact_bwd_finalize_into(part.data_ptr(), bpg, groups, c, sums.data_ptr(),
+                                                               g_t.data_ptr(), b_t.data_ptr(), g_t.numel(), int(accumulate), _stream()),
+                           "normact_bwd_finalize")
+            else:
+                _lib.check(lib.mi355_normact_bwd_finalize(part.data_ptr(), bpg, groups, c, sums.data_ptr(),
+                                                          g_t.data_ptr(), b_t.data_ptr(), _stream()), "normact_bwd_finalize")
+            dgamma, dbeta = (None, None) if owned else (g_t, b_t)
+            d.sums = sums.data_ptr()
+        _lib.check(lib.mi355_normact_bwd_apply(C.byref(d), _stream()), "normact_bwd_apply")
     return dz, dgamma, dbeta
 
 
@@ -853,16 +865,13 @@ def normact_small_fwd(z, groups, gamma, beta, eps, slope, drop_p=0.0, seed=0, se
     d.base = _normact_desc(z, groups, None, None, gamma, beta, slope, drop_p, seed, seed_t, alpha)
     d.base.a, d.base.lda = out.data_ptr(), act_ld(out)
     if s2d:
-        d.base.s2d_a = 1
-        d.base.sd, d.base.sh, d.base.sw = z.shape[1:4]
+        _set_extents(d.base, z, "s2d_a")
     d.eps, d.momentum = eps, momentum
     d.mean_out, d.rstd_out = mean.data_ptr(), rstd.data_ptr()
     d.running_mean, d.running_var, d.batches_tracked = _ptr(running_mean), _ptr(running_var), _ptr(batches_tracked)
     d.n_real = running_mean.numel() if running_mean is not None else 0
-    after = _norm_probe("fwd", z, gamma)
-    _lib.check(_lib.load().mi355_normact_small_fwd(C.byref(d), _stream()), "normact_small_fwd")
-    if after is not None:
-        after()
+    with _norm_probed("fwd", z, gamma):
+        _lib.check(_lib.load().mi355_normact_small_fwd(C.byref(d), _stream()), "normact_small_fwd")
     return out, mean, rstd
 
 
@@ -879,31 +888,21 @@ def normact_small_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, see
     d = _lib.NormSmallDesc()
     d.base = _normact_desc(z, groups, mean, rstd, gamma, beta, slope, drop_p, seed, seed_t, alpha)
     if dalpha is not None:
-        require_cuda(dalpha)
-        if alpha is None:
-            raise ValueError("normact_small_bwd: a slope gradient needs the slope on the device (alpha)")
-        if accumulate and affine_into is None:
-            raise ValueError("normact_small_bwd: accumulate goes with affine_into (fresh affine gradients have nothing to add to)")
-        assert dalpha.dtype == torch.float32 and dalpha.numel() == 1
+        _check_dalpha("normact_small_bwd", dalpha, alpha, affine_into, accumulate)
         d.base.dalpha = dalpha.data_ptr()
     d.base.da, d.base.ldda = da.data_ptr(), act_ld(da)
     dz = torch.empty(z.shape, dtype=z.dtype, device=z.device)
     d.base.dz, d.base.lddz = dz.data_ptr(), act_ld(dz)
     d.base.batch_stats = 1 if batch_stats else 0
     if s2d:
-        d.base.s2d_da = 1
-        d.base.sd, d.base.sh, d.base.sw = z.shape[1:4]
+        _set_extents(d.base, z, "s2d_da")
     dgamma = dbeta = None
-    if affine_into is not None:
-        g_into, b_into = affine_into
-        require_cuda(g_into, b_into)
-        assert g_into.dtype == b_into.dtype == torch.float32 and g_into.numel() == b_into.numel() <= c
-        d.base.n_affine = g_into.numel()
-        d.dgamma, d.dbeta, d.accumulate = g_into.data_ptr(), b_into.data_ptr(), 1 if accumulate else 0
-    elif want_affine:
-        dgamma = torch.zeros((c,), dtype=torch.float32, device=z.device)
-        dbeta = torch.zeros((c,), dtype=torch.float32, device=z.device)
-        d.dgamma, d.dbeta, d.accumulate = dgamma.data_ptr(), dbeta.data_ptr(), 0
+    if affine_into is not None or want_affine:
+        g_t, b_t, owned = _affine_targets(z, affine_into, torch.zeros)
+        d.dgamma, d.dbeta, d.accumulate = g_t.data_ptr(), b_t.data_ptr(), int(owned and accumulate)
+        if owned:
+            d.base.n_affine = g_t.numel()
+        dgamma, dbeta = (None, None) if owned else (g_t, b_t)
     # three or more statistic groups (the reference's batch of 8 patches): scratch for the per-group sums, so that the chunks of
     # groups run as independent workgroups and a second tiny launch sums the affine gradients over the groups (same order, f64).
     # A slope gradient: the same scratch holds its per-group, per-channel totals ([groups][c] doubles, the first half) instead
@@ -914,10 +913,8 @@ def normact_small_bwd(z, da, groups, mean, rstd, gamma, beta, slope, drop_p, see
             d.base.dalpha_part = gpart.data_ptr()
         else:
             d.base.part = gpart.data_ptr()
-    after = _norm_probe("bwd", z, gamma)
-    _lib.check(_lib.load().mi355_normact_small_bwd(C.byref(d), _stream()), "normact_small_bwd")
-    if after is not None:
-        after()
+    with _norm_probed("bwd", z, gamma):
+        _lib.check(_lib.load().mi355_normact_small_bwd(C.byref(d), _stream()), "normact_small_bwd")
     return dz, dgamma, dbeta
 
 
